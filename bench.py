@@ -17,11 +17,17 @@ nfn_set_launch_events hook, hipExtLaunchKernel): no marker packets sit between t
 steps, so the wall clock (`value`) carries no timing overhead (`--event-mode marker`: the
 older hipEventRecord pair around every step).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C5|C3P]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C5|C3P] [--full]
+                  [--dump-outputs DIR]
                   [--mode forward|grad|dense|dense_grad|bijector|flows [--flow-params views|separate|strided]]
   N > 1: either under a launcher (python -m torch.distributed.run --nproc-per-node N ...
   bench.py --gpus N), or plain `python bench.py --gpus N`, which starts that launcher as a
   child process itself (before touching the GPU) and exits with its status.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what
+takes runs of its own: the CPU baseline (`cpu_baseline`, rank 0 at N = 1) and, for the
+fused Dense and bijector modes, the unfused comparison (`unfused_ms`); without it both are
+null.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -250,6 +256,38 @@ def load_traffic(cfg: str, B: int):
     return float(rec["hbm_bytes_per_launch"]), os.path.relpath(cands[-1], REPO)
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per array: at most seven arrays, well under 64 MB in all
+DUMP_SEED = 22
+
+
+def dump_outputs(out_dir: str, launcher, scalars: dict) -> list:
+    """--dump-outputs: the arrays the timed path's last step left in the launcher's output
+    buffers (what a caller of that launcher reads after ``launch()``) as ``<name>.npy``,
+    float32, and the step's scalars as float64.  An output of more than DUMP_MAX_ELEMS
+    elements is written as a fixed sample of its flattened form: the elements at
+    ``sort(default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_ELEMS))``, the same for every run
+    of the same shape.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for attr, name in (("out", "log_prob"), ("logp", "log_prob"), ("grad_t", "grad_t"), ("grad_y", "grad_y"),
+                       ("grad_h", "grad_h"), ("grad_W", "grad_W"), ("grad_b", "grad_b"), ("z_out", "z_out"),
+                       ("ldj", "ldj")):
+        ten = getattr(launcher, attr, None)
+        if not isinstance(ten, torch.Tensor):
+            continue
+        n = ten.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_ELEMS))
+            ten = ten.reshape(-1)[torch.as_tensor(idx, device=ten.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), ten.detach().cpu().numpy().astype(np.float32, copy=False))
+        names.append(name)
+    for name, val in scalars.items():
+        if val is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray([val], np.float64))
+            names.append(name)
+    return names
+
+
 def spawn_ranks(args) -> int:
     """`--gpus N` (N > 1) without a launcher: run N ranks as a CHILD
     `torch.distributed.run` (one process per GPU, 127.0.0.1 rendezvous) with the same
@@ -291,7 +329,14 @@ def main():
                          "so a short warmup would time the ramp, not the steady state (0 disables)")
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="override the per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (cpu_baseline) and, "
+                         "for --mode dense / dense_grad / bijector, the unfused comparison (unfused_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output arrays of the last timed step as "
+                         "DIR/<name>.npy (float32; the step's sum / non-finite count as float64; a fixed "
+                         "seeded sample of an output above 2^20 elements; rank 0's shard at N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--diag", action="store_true",
                     help="bind libnfn_hip_diag.so (NFN_* knobs, e.g. NFN_ABLATE_FLOWS=1): A/B studies only, "
                          "never a reported line")
@@ -543,53 +588,6 @@ def main():
         kt = torch.tensor([kern_ms], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(kt, op=dist.ReduceOp.MAX)
         kern_ms = float(kt.item())
-    unfused_ms = None
-    if args.mode == "dense" and rank == 0:
-        # the same x->density work unfused: t = h W + b by the library GEMM (t written to
-        # HBM), then the chain kernel over t (read back) — what the fusion replaces
-        t_buf = torch.empty((B, P) if S is None else (S, B, P), dtype=torch.float32, device=dev)
-        plain = ops.ChainLauncher(y, t_buf, ft, d, True, write_values=True, draws=S)
-
-        def unfused():
-            if S is None:
-                torch.addmm(bd, h, Wd, out=t_buf)
-            else:
-                torch.baddbmm(bd[:, None, :], h, Wd, out=t_buf)
-            plain.launch(sh)
-    elif args.mode == "dense_grad" and rank == 0:
-        # unfused: t by the library GEMM, the chain backward kernel, library GEMMs for dh / dW, db
-        t_buf = torch.empty((B, P), dtype=torch.float32, device=dev)
-        plain = ops.GradLauncher(y, t_buf, ft, d, True, g_out=g_up)
-
-        def unfused():
-            torch.addmm(bd, h, Wd, out=t_buf)
-            plain.launch(sh)
-            gt = plain.grad_t
-            return gt @ Wd.t(), h.t() @ gt, gt.sum(0)
-    elif args.mode == "bijector" and rank == 0:
-        # the same Chain through the flow-by-flow Bijector path (one single-flow launch per
-        # flow: each reads its block's cache lines of t again)
-        from normalizingflownetwork_amd import InverseNormalizingFlowLayer
-        from normalizingflownetwork_amd.normalizing_flows import Chain
-
-        flows = InverseNormalizingFlowLayer._get_bijector(t[:, 2 * d:], ft, d).bijectors
-        steps = Chain([type(f)(f.params, d) for f in flows])
-        steps._fused = lambda x=None: None
-
-        def unfused():
-            steps.forward_and_log_det_jacobian(y)
-    if (dense_mode or args.mode == "bijector") and rank == 0:
-        for _ in range(3):
-            unfused()
-        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-        for e0, e1 in pairs:
-            e0.record(stream)
-            unfused()
-            e1.record(stream)
-        torch.cuda.synchronize()
-        unfused_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in pairs]))
-        if dense_mode:
-            del t_buf, plain
     nonfinite = None
     if grad_mode or args.mode in ("bijector", "flows", "grid"):
         mean_ll = None
@@ -603,6 +601,58 @@ def main():
     else:
         mean_ll = float(launcher.sum.item()) / B
         nonfinite = int(launcher.nonfinite.item())
+    # --dump-outputs: what the last timed step left in the launcher's buffers, before any further launch
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, launcher, {"mean_log_prob": mean_ll, "nonfinite_log_prob": nonfinite})
+    unfused_ms = None
+    compare = args.full and rank == 0  # the unfused comparison: runs of its own
+    if args.mode == "dense" and compare:
+        # the same x->density work unfused: t = h W + b by the library GEMM (t written to
+        # HBM), then the chain kernel over t (read back) — what the fusion replaces
+        t_buf = torch.empty((B, P) if S is None else (S, B, P), dtype=torch.float32, device=dev)
+        plain = ops.ChainLauncher(y, t_buf, ft, d, True, write_values=True, draws=S)
+
+        def unfused():
+            if S is None:
+                torch.addmm(bd, h, Wd, out=t_buf)
+            else:
+                torch.baddbmm(bd[:, None, :], h, Wd, out=t_buf)
+            plain.launch(sh)
+    elif args.mode == "dense_grad" and compare:
+        # unfused: t by the library GEMM, the chain backward kernel, library GEMMs for dh / dW, db
+        t_buf = torch.empty((B, P), dtype=torch.float32, device=dev)
+        plain = ops.GradLauncher(y, t_buf, ft, d, True, g_out=g_up)
+
+        def unfused():
+            torch.addmm(bd, h, Wd, out=t_buf)
+            plain.launch(sh)
+            gt = plain.grad_t
+            return gt @ Wd.t(), h.t() @ gt, gt.sum(0)
+    elif args.mode == "bijector" and compare:
+        # the same Chain through the flow-by-flow Bijector path (one single-flow launch per
+        # flow: each reads its block's cache lines of t again)
+        from normalizingflownetwork_amd import InverseNormalizingFlowLayer
+        from normalizingflownetwork_amd.normalizing_flows import Chain
+
+        flows = InverseNormalizingFlowLayer._get_bijector(t[:, 2 * d:], ft, d).bijectors
+        steps = Chain([type(f)(f.params, d) for f in flows])
+        steps._fused = lambda x=None: None
+
+        def unfused():
+            steps.forward_and_log_det_jacobian(y)
+    if (dense_mode or args.mode == "bijector") and compare:
+        for _ in range(3):
+            unfused()
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        for e0, e1 in pairs:
+            e0.record(stream)
+            unfused()
+            e1.record(stream)
+        torch.cuda.synchronize()
+        unfused_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in pairs]))
+        if dense_mode:
+            del t_buf, plain
 
     if rank == 0:
         total_evals = evals_per_step * world * args.steps
@@ -632,7 +682,7 @@ def main():
                                                            "flows": "_flows" if args.flow_params == "views" else "_flows_" + args.flow_params
                                                            }.get(args.mode, ""), B)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline({"flows": "bijector", "grid": "forward"}.get(args.mode, args.mode), args.config, H=H,
                                seconds=args.cpu_seconds)
         wl = {
@@ -740,6 +790,8 @@ def main():
             "mean_log_prob": mean_ll,
             "nonfinite_log_prob": nonfinite,
             "unfused_ms": unfused_ms,
+            "full": args.full,
+            **({"dumped_outputs": dumped} if dumped is not None else {}),
             "nfn_env": nfn_env,
             **({"library": "libnfn_hip_diag.so (--diag: A/B study, not a reported line)"} if args.diag else {}),
         }

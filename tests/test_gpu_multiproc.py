@@ -84,6 +84,39 @@ def test_bench_spawns_its_ranks(gpu):
     assert np.isfinite(out["mean_log_prob"]) and out["nonfinite_log_prob"] == 0
 
 
+def test_bench_plain_run_dumps_its_outputs(gpu, tmp_path):
+    """A plain run (no --full) measures no CPU baseline, times exactly --steps steps, and
+    --dump-outputs writes what its launcher computed from the seeded inputs: the same bits
+    as the same launcher over the same generator's inputs here."""
+    import torch
+
+    from normalizingflownetwork_amd import ops
+
+    B = (1 << 18) + 3
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--prewarm-ms", "0", "--batch", str(B), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["full"] is False and out["cpu_baseline"] is None and out["unfused_ms"] is None
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(B / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    assert out["dumped_outputs"] == ["log_prob", "mean_log_prob", "nonfinite_log_prob"]
+    lp = np.load(tmp_path / "out" / "log_prob.npy")
+    assert lp.dtype == np.float32 and lp.shape == (B,)
+    assert np.load(tmp_path / "out" / "mean_log_prob.npy").tolist() == [out["mean_log_prob"]]
+    assert np.load(tmp_path / "out" / "nonfinite_log_prob.npy").tolist() == [0.0]
+    flows = ("planar", "radial") * 5
+    gen = torch.Generator(device=gpu).manual_seed(22)
+    y = torch.randn((B, 1), generator=gen, device=gpu)
+    t = torch.randn((B, ops.total_param_size(flows, 1, True)), generator=gen, device=gpu)
+    launcher = ops.ChainLauncher(y, t, flows, 1, True, write_values=True)
+    launcher.launch()
+    torch.cuda.synchronize()
+    assert np.array_equal(lp, launcher.out.cpu().numpy())
+    assert float(launcher.sum.item()) / B == out["mean_log_prob"]
+
+
 def test_two_rank_reduction_matches_one_rank(gpu):
     """The all-reduced mean over two ranks' shards equals one launch over the concatenated
     batch (fp64, rel 1e-12), and the non-finite counts add up across ranks."""

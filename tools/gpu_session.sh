@@ -38,7 +38,7 @@ for s in $STEPS; do
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 240 --timeout-method thread ;;
     testsx) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 240 --timeout-method thread ;;
     smoke) run smoke 240 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 240 python bench.py --steps 50 --warmup 10 ;;
+    bench) run bench 240 python bench.py --full --steps 50 --warmup 10 ;;
     bench20) run bench20 240 python bench.py --gpus 1 --steps 20 --warmup 5 ;;  # the driver's command
     bench_nocpu) run bench_nocpu 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline ;;
     c3) run bench_c3 300 python bench.py --config C3 --steps 50 --warmup 10 --no-cpu-baseline ;;
@@ -57,11 +57,11 @@ for s in $STEPS; do
         python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline; cd "$ROOT"; }
       { cd /tmp; run pmc_write 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -o w -- \
         python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline; cd "$ROOT"; } ;;
-    dgrad) run bench_dense_grad 300 python bench.py --mode dense_grad --steps 20 --warmup 5 --cpu-seconds 8 ;;
+    dgrad) run bench_dense_grad 300 python bench.py --full --mode dense_grad --steps 20 --warmup 5 --cpu-seconds 8 ;;
     prof_dgrad)
       { cd /tmp; run rocprof_dgrad 200 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$OUT/prof_dgrad" -o dgrad -- \
         python3 "$ROOT/bench.py" --mode dense_grad --steps 20 --warmup 5 --no-cpu-baseline; cd "$ROOT"; } ;;
-    grad) run bench_grad_c2 300 python bench.py --mode grad --steps 20 --warmup 5 --cpu-seconds 8 ;;
+    grad) run bench_grad_c2 300 python bench.py --full --mode grad --steps 20 --warmup 5 --cpu-seconds 8 ;;
     grad_c3) run bench_grad_c3 300 python bench.py --mode grad --config C3 --steps 20 --warmup 5 --no-cpu-baseline ;;
     prof_grad)
       { cd /tmp; run rocprof_grad 200 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$OUT/prof_grad" -o grad -- \
@@ -91,7 +91,7 @@ for s in $STEPS; do
     mode) run mode 300 python tools/microbench.py mode ;;
     valu) run valu 300 python tools/microbench.py valu ;;
     c3micro) run c3micro 300 python tools/microbench.py c3 ;;
-    dense) run bench_dense 300 python bench.py --mode dense --steps 50 --warmup 10 --cpu-seconds 6 ;;
+    dense) run bench_dense 300 python bench.py --full --mode dense --steps 50 --warmup 10 --cpu-seconds 6 ;;
     densetests) run densetests 300 python -u -m pytest tests/test_gpu_dense.py -m gpu -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     diagtests) run diagtests 300 python -u -m pytest tests/test_gpu_diag.py -m gpu -v -s -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     gradtests) run gradtests 300 python -u -m pytest tests/test_gpu_grad.py -m gpu -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
@@ -108,7 +108,7 @@ for s in $STEPS; do
         python3 "$ROOT/bench.py" --config C5 --steps 5 --warmup 2 --no-cpu-baseline; cd "$ROOT"; }
       { cd /tmp; run pmc_write_c5 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write_c5" -o w -- \
         python3 "$ROOT/bench.py" --config C5 --steps 5 --warmup 2 --no-cpu-baseline; cd "$ROOT"; } ;;
-    dense_c5) run bench_dense_c5 300 python bench.py --mode dense --config C5 --steps 50 --warmup 10 --cpu-seconds 8 ;;
+    dense_c5) run bench_dense_c5 300 python bench.py --full --mode dense --config C5 --steps 50 --warmup 10 --cpu-seconds 8 ;;
     prof_dense_c5)
       { cd /tmp; run rocprof_dense_c5 200 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$OUT/prof_dense_c5" -o densec5 -- \
         python3 "$ROOT/bench.py" --mode dense --config C5 --steps 20 --warmup 5 --no-cpu-baseline; cd "$ROOT"; } ;;
@@ -162,12 +162,12 @@ for s in $STEPS; do
         { cd /tmp; run pmc_lds_$i 90 timeout -s KILL 80 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d "$OUT/pmc_lds_$i" -o l -- \
           python3 "$ROOT/bench.py" $args --steps 3 --warmup 1 --prewarm-ms 0 --no-cpu-baseline; cd "$ROOT"; }
       done ;;
-    bijector) run bench_bijector 300 python bench.py --mode bijector --steps 30 --warmup 5 --cpu-seconds 6 ;;
+    bijector) run bench_bijector 300 python bench.py --full --mode bijector --steps 30 --warmup 5 --cpu-seconds 6 ;;
     r2) run bench_r2 200 python bench.py --config R2 --steps 50 --warmup 10 --no-cpu-baseline ;;
     r10) run bench_r10 200 python bench.py --config R10 --steps 50 --warmup 10 --no-cpu-baseline ;;
     grid) run bench_grid 200 python bench.py --mode grid --steps 30 --warmup 5 --no-cpu-baseline ;;
     flows) run bench_flows 300 python bench.py --mode flows --steps 20 --warmup 5 --no-cpu-baseline ;;
-    dense_c3p) run bench_dense_c3p 300 python bench.py --mode dense --config C3P --steps 20 --warmup 5 --no-cpu-baseline ;;
+    dense_c3p) run bench_dense_c3p 300 python bench.py --full --mode dense --config C3P --steps 20 --warmup 5 --no-cpu-baseline ;;
     pairtests) run pairtests 300 python -u -m pytest tests/test_gpu_pairs.py -m gpu -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     parity) run parity 300 python -u -m pytest tests/test_gpu_parity.py -m gpu -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     sampleerr) run sampleerr 200 python tools/sample_err.py ;;
@@ -186,7 +186,7 @@ for s in $STEPS; do
       { cd /tmp; run pmc_write_bij 120 timeout -s KILL 100 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write_bij" -o w -- \
         python3 "$ROOT/bench.py" --mode bijector --steps 5 --warmup 2 --no-cpu-baseline; cd "$ROOT"; } ;;
     mptests) run mptests 400 python -u -m pytest tests/test_gpu_multiproc.py tests/test_gpu_comm.py -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    bijector_c3) run bench_bijector_c3 300 python bench.py --mode bijector --config C3 --steps 30 --warmup 5 --cpu-seconds 6 ;;
+    bijector_c3) run bench_bijector_c3 300 python bench.py --full --mode bijector --config C3 --steps 30 --warmup 5 --cpu-seconds 6 ;;
     fitbench) run fitbench 300 python tools/fit_bench.py ;;
     traintests) run traintests 400 python -u -m pytest tests/test_gpu_training.py -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     sweep) run sweep 300 python tools/microbench.py sweep ;;
