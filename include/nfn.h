@@ -101,7 +101,9 @@ extern "C" {
 #define NFN_COMM_ID_BYTES 128
 
 /* Library version as MAJOR*10000 + MINOR*100 + PATCH.
- *   203 (0.2.3): + nfn_set_launch_events (additive, measurement hook).
+ *   203 (0.2.3): + nfn_set_launch_events (additive, measurement hook); later also, with
+ *                no version change (additive, every earlier entry unchanged), the four
+ *                nfn_kernel_mixture_* entries.
  *   202 (0.2.2): + nfn_flow_vjp_f32 (additive).
  *   201 (0.2.1): + nfn_split_blocks_f32 (additive; every 200 entry point unchanged).
  *   200 (0.2.0): out_sum is a device double[2] {sum, non-finite count} (was double[1]);
@@ -347,6 +349,49 @@ int32_t nfn_posterior_lse_dense_f32(const float* y, int64_t y_bstride, const flo
                                     const int32_t* flow_ids, int32_t K, int32_t trainable_base, const float* y_mean,
                                     const float* y_std, float* out_lse, double* out_sum, double* workspace,
                                     void* stream);
+
+/*
+ * Kernel mixture network density (GaussianKernelsLayer, estimators/DistributionLayers.py:74-172):
+ * a mixture of M = n_centers * n_scales isotropic Gaussian kernels whose weights are the
+ * softmax of a per-sample logit row, in ONE streaming pass over the logits:
+ *   c_bk        = -0.5 * sum_j ((y_bj - locs_kj) / s_k)^2 - d*log|s_k| - 0.5*d*log(2*pi)
+ *   out_logp[b] = logsumexp_k(logits_bk + c_bk) - logsumexp_k(logits_bk)  [- sum_j log y_std_j]
+ * (y_b replaced by (y_b - y_mean) / y_std when given).
+ *   y       : (B or 1, d) rows at y_bstride floats (0 = broadcast)
+ *   logits  : (B, M) rows at logits_rowstride floats (>= M: a column view of a wider tensor works)
+ *   locs    : (M, d) row-major kernel centres;  scales : (M,) bandwidths s_k
+ *   out_logp (nullable), out_sum (nullable), workspace : as for nfn_chain_logprob_f32, with
+ *             workspace a device double[nfn_kernel_mixture_workspace_doubles(B, d, M)]
+ * QUIRK kept from the reference: its bandwidth softplus(v) + log(expm1(init)) is NOT a
+ * softplus-inverse parametrisation and is negative at the defaults (v = 0, init = 0.3 gives
+ * -0.3571).  TFP's MultivariateNormalDiag evaluates it through log|s| and (./s)^2, so the
+ * density is that of |s_k|: |s| enters the log term only, s itself everything else (the
+ * gradient below is d/ds of exactly this expression).
+ * A -inf logit removes its component; a row of all -inf, any +inf and any NaN logit give a
+ * non-finite out_logp, which out_sum[1] counts.
+ * Limits: 1 <= M <= 1024, 1 <= d <= NFN_MAX_DIMS, M * d <= 8192 (else NFN_E_SHAPE).
+ *
+ * Backward, for L = sum_b g_out[b] * out_logp[b] (g_out NULL = ones), with
+ * post = softmax_k(logits + c), prior = softmax_k(logits):
+ *   grad_logits[b, k] = g_b * (post_bk - prior_bk)          (B, M) at grad_logits_rowstride >= M
+ *   grad_y[b, j]      = g_b * sum_k post_bk * (locs_kj - y_bj) / s_k^2  [/ y_std_j]   (B, d) contiguous
+ *   grad_scales[k]    = sum_b g_b * post_bk * (r2_bk / s_k^3 - d / s_k),  r2_bk = sum_j (y_bj - locs_kj)^2
+ * Every output is nullable.  grad_scales (M,) is overwritten: per-workgroup partials in
+ * workspace (device float[nfn_kernel_mixture_grad_workspace_floats(B, d, M)], needed with
+ * grad_scales) and a fixed-order final sum, bitwise deterministic.
+ */
+int64_t nfn_kernel_mixture_workspace_doubles(int64_t B, int32_t d, int32_t M);
+int32_t nfn_kernel_mixture_logprob_f32(const float* y, int64_t y_bstride, const float* logits,
+                                       int64_t logits_rowstride, const float* locs, const float* scales, int64_t B,
+                                       int32_t d, int32_t M, const float* y_mean, const float* y_std,
+                                       float* out_logp, double* out_sum, double* workspace, void* stream);
+int64_t nfn_kernel_mixture_grad_workspace_floats(int64_t B, int32_t d, int32_t M);
+int32_t nfn_kernel_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, const float* logits,
+                                            int64_t logits_rowstride, const float* locs, const float* scales,
+                                            int64_t B, int32_t d, int32_t M, const float* y_mean, const float* y_std,
+                                            const float* g_out, float* out_logp, float* grad_logits,
+                                            int64_t grad_logits_rowstride, float* grad_y, float* grad_scales,
+                                            float* workspace, void* stream);
 
 /*
  * Multi-GPU (one process per GPU, batch sharded over ranks).  The communicator

@@ -5,6 +5,7 @@ Layout:
   csrc/                  HIP kernels for gfx950 + the extern "C" ABI (include/nfn.h):
                          nfn_persistent / nfn_group / nfn_tile (forward, posterior),
                          nfn_grad (fused backward), nfn_misc (reductions),
+                         nfn_mixture (kernel mixture log_prob, forward + backward),
                          nfn_comm (RCCL all-reduce), nfn_api (validation + dispatch)
   build.py               parallel hipcc build of libnfn_hip.so (in-tree)
   _lib.py                ctypes binding of libnfn_hip.so (no CPU fallback)
@@ -18,8 +19,9 @@ Layout:
   parallel.py            batch-sharded multi-GPU mean log-likelihood (RCCL all-reduce)
 """
 
-from .distribution_layers import FlowDistribution, InverseNormalizingFlowLayer, TensorShape
-from .estimators import BayesNormalizingFlowNetwork, NormalizingFlowNetwork
+from .distribution_layers import (FlowDistribution, GaussianKernelsLayer, InverseNormalizingFlowLayer,
+                                  KernelMixtureDistribution, TensorShape)
+from .estimators import BayesNormalizingFlowNetwork, KernelMixtureNetwork, NormalizingFlowNetwork
 from .normalizing_flows import FLOWS, AffineFlow, Bijector, Chain, Invert, PlanarFlow, RadialFlow
 
 __version__ = "0.1.0"
@@ -37,4 +39,7 @@ __all__ = [
     "TensorShape",
     "NormalizingFlowNetwork",
     "BayesNormalizingFlowNetwork",
+    "GaussianKernelsLayer",
+    "KernelMixtureDistribution",
+    "KernelMixtureNetwork",
 ]

@@ -49,6 +49,8 @@ UNITS = [
     ("dense_hp3", "nfn_dense.hip", ["-DNFN_DENSE_HP=3"]),
     ("dense_hp4", "nfn_dense.hip", ["-DNFN_DENSE_HP=4"]),
     ("dense_grad", "nfn_dense_grad.hip", []),
+    ("mixture_fast", "nfn_mixture.hip", ["-DNFN_FAST=1"]),
+    ("mixture_precise", "nfn_mixture.hip", ["-DNFN_FAST=0"]),
     ("sample", "nfn_sample.hip", []),
     ("comm", "nfn_comm.hip", []),
 ]

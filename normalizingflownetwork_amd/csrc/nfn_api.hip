@@ -812,6 +812,73 @@ int32_t run_grid(const float* y_grid, int64_t y_gstride, int32_t G, const float*
   return check_hip("chain_grid_kernel launch");
 }
 
+// Gaussian-kernel mixture (nfn_mixture.hip).  The persistent grid never exceeds
+// kMixMaxParts workgroups, and a tile holds at least 4 rows: ONE function sizes both
+// workspaces and caps every launch.
+constexpr int64_t kMixMaxParts = 2048;
+int64_t mixture_parts(int64_t B) { return std::max<int64_t>(1, std::min<int64_t>(kMixMaxParts, (B + 3) / 4)); }
+
+int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* logits, int64_t logits_rowstride,
+                    const float* locs, const float* scales, int64_t B, int32_t d, int32_t M, const float* y_mean,
+                    const float* y_std, const float* g_out, float* out_logp, double* out_sum, double* workspace,
+                    float* grad_logits, int64_t grad_logits_rowstride, float* grad_y, float* grad_scales,
+                    float* grad_workspace, void* stream) {
+  g_last_error.clear();
+  const HookScope hook_scope;
+  if (M < 1 || M > 1024) return fail(NFN_E_SHAPE, "number of kernels M must be in 1..1024");
+  if (d < 1 || d > NFN_MAX_DIMS) return fail(NFN_E_SHAPE, "n_dims out of range");
+  if ((int64_t)M * d > 8192) return fail(NFN_E_SHAPE, "M * n_dims must be <= 8192 (the centres are staged in LDS)");
+  if (B < 0) return fail(NFN_E_SHAPE, "batch size must be >= 0");
+  if (y_bstride < 0 || (y_bstride != 0 && y_bstride < d)) return fail(NFN_E_SHAPE, "bad y batch stride");
+  if (logits_rowstride < M) return fail(NFN_E_SHAPE, "logits row stride < M");
+  if (grad && grad_logits && grad_logits_rowstride < M) return fail(NFN_E_SHAPE, "grad_logits row stride < M");
+  if ((y_mean == nullptr) != (y_std == nullptr)) return fail(NFN_E_NULLPTR, "y_mean and y_std must both be given or both NULL");
+  if (!y || !logits || !locs || !scales) return fail(NFN_E_NULLPTR, "y, logits, locs or scales is NULL");
+  if (out_sum && !workspace) return fail(NFN_E_NULLPTR, "workspace is NULL but out_sum requested");
+  if (grad_scales && !grad_workspace) return fail(NFN_E_NULLPTR, "workspace is NULL but grad_scales requested");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (B == 0) {
+    if (out_sum && hipMemsetAsync(out_sum, 0, 2 * sizeof(double), s) != hipSuccess) return check_hip("hipMemsetAsync");
+    if (grad_scales && hipMemsetAsync(grad_scales, 0, sizeof(float) * M, s) != hipSuccess) return check_hip("hipMemsetAsync");
+    return NFN_OK;
+  }
+  MixArgs a;
+  memset(&a, 0, sizeof(a));
+  a.y = y;
+  a.logits = logits;
+  a.locs = locs;
+  a.scales = scales;
+  a.y_mean = y_mean;
+  a.y_std = y_std;
+  a.g_out = g_out;
+  a.out = out_logp;
+  a.y_bstride = y_bstride;
+  a.rs = logits_rowstride;
+  a.B = B;
+  a.d = d;
+  a.M = M;
+  a.grid_cap = mixture_parts(B);
+  if (grad) {
+    a.grad_logits = grad_logits;
+    a.gl_rs = grad_logits ? grad_logits_rowstride : 0;
+    a.grad_y = grad_y;
+    a.part = grad_scales ? grad_workspace : nullptr;
+  } else if (workspace) {
+    a.partials = workspace + 2;
+    a.out_sum = out_sum;
+    a.epoch = out_sum ? next_epoch() : 0u;
+  }
+  const size_t lds = sizeof(float) * ((size_t)3 * M + (size_t)M * d);
+  const int64_t grid = use_fast_math() ? launch_mixture_fast(grad, a, lds, s) : launch_mixture_precise(grad, a, lds, s);
+  if (grid <= 0) return fail(NFN_E_SHAPE, "no kernel mixture instance for this shape");
+  int32_t rc = check_hip("kernel_mixture_kernel launch");
+  if (rc == NFN_OK && grad && grad_scales) {
+    launch_sum_partials(a.part, grid, M, grad_scales, nullptr, M, s);
+    rc = check_hip("sum_partials_kernel launch");
+  }
+  return rc;
+}
+
 }  // namespace
 }  // namespace nfn
 
@@ -922,6 +989,38 @@ int32_t nfn_chain_logprob_dense_grad_f32(const float* y, int64_t y_bstride, cons
                                          float* grad_b, float* grad_y, float* workspace, void* stream) {
   return run_dense_grad(y, y_bstride, h, h_rowstride, H, W, bias, B, d, flow_ids, K, trainable_base, y_mean, y_std,
                         g_out, out_logp, grad_h, grad_h_rowstride, grad_W, grad_b, grad_y, workspace, stream);
+}
+
+int64_t nfn_kernel_mixture_workspace_doubles(int64_t B, int32_t d, int32_t M) {
+  (void)d;
+  (void)M;
+  if (B <= 0) return 0;
+  return 2 + 2 * mixture_parts(B);  // [count | ticket | (sum, count) pairs]
+}
+
+int32_t nfn_kernel_mixture_logprob_f32(const float* y, int64_t y_bstride, const float* logits,
+                                       int64_t logits_rowstride, const float* locs, const float* scales, int64_t B,
+                                       int32_t d, int32_t M, const float* y_mean, const float* y_std,
+                                       float* out_logp, double* out_sum, double* workspace, void* stream) {
+  return run_mixture(false, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std, nullptr,
+                     out_logp, out_sum, workspace, nullptr, 0, nullptr, nullptr, nullptr, stream);
+}
+
+int64_t nfn_kernel_mixture_grad_workspace_floats(int64_t B, int32_t d, int32_t M) {
+  (void)d;
+  if (B <= 0 || M <= 0) return 0;
+  return (int64_t)M * mixture_parts(B);  // one grad_scales partial row per workgroup
+}
+
+int32_t nfn_kernel_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, const float* logits,
+                                            int64_t logits_rowstride, const float* locs, const float* scales,
+                                            int64_t B, int32_t d, int32_t M, const float* y_mean, const float* y_std,
+                                            const float* g_out, float* out_logp, float* grad_logits,
+                                            int64_t grad_logits_rowstride, float* grad_y, float* grad_scales,
+                                            float* workspace, void* stream) {
+  return run_mixture(true, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std, g_out,
+                     out_logp, nullptr, nullptr, grad_logits, grad_logits_rowstride, grad_y, grad_scales, workspace,
+                     stream);
 }
 
 int32_t nfn_posterior_lse_dense_f32(const float* y, int64_t y_bstride, const float* h, int64_t h_drawstride,

@@ -206,6 +206,35 @@ bool launch_dense1_hpair_4(bool post, const DenseArgs& da, hipStream_t s, int64_
 // nfn_dense_grad.hip: returns the number of per-workgroup partials written (0 = no instance)
 int64_t launch_dense_grad(bool fast, int dm, const DenseGradArgs& g, size_t lds, int64_t max_parts, hipStream_t s);
 void launch_sum_partials(const float* part, int64_t nparts, int n, float* gW, float* gb, int nW, hipStream_t s);
+// nfn_mixture.hip (compiled once per math mode): the Gaussian-kernel mixture log_prob
+// (nfn_kernel_mixture_logprob_f32) and its backward
+struct MixArgs {
+  const float* y;        // (B or 1, d) rows at y_bstride floats
+  const float* logits;   // (B, M) rows at rs floats
+  const float* locs;     // (M, d) row-major
+  const float* scales;   // (M,)
+  const float* y_mean;   // (d,) or NULL
+  const float* y_std;
+  const float* g_out;    // backward: upstream gradient (B,) or NULL = ones
+  float* out;            // (B,) log_prob, or NULL
+  double* partials;      // forward: the workspace's (sum, count) pairs, or NULL
+  double* out_sum;
+  float* grad_logits;    // (B, M) rows at gl_rs floats, or NULL
+  float* grad_y;         // (B, d) contiguous, or NULL
+  float* part;           // backward: per-workgroup grad_scales partials (grid x M), or NULL
+  int64_t y_bstride;
+  int64_t rs;
+  int64_t gl_rs;
+  int64_t B;
+  int64_t ntiles;        // set by the launcher: tiles of (256 / G) * rows-per-group rows
+  int64_t grid_cap;      // the workspace's partial slots
+  int32_t d;
+  int32_t M;
+  uint32_t epoch;
+};
+// launches the (G, NV) instance for M; returns the grid (= number of partials written)
+int64_t launch_mixture_fast(bool grad, const MixArgs& a, size_t lds, hipStream_t s);
+int64_t launch_mixture_precise(bool grad, const MixArgs& a, size_t lds, hipStream_t s);
 // nfn_sample.hip
 void launch_sample(bool fast, int dm, const SampleArgs& sa, dim3 grid, dim3 block, size_t lds, hipStream_t s);
 // nfn_grid.hip

@@ -1,0 +1,269 @@
+// nfn_mixture.hip — the kernel mixture network's density layer (GaussianKernelsLayer,
+// estimators/DistributionLayers.py:74-172): log_prob of a mixture of M = n_centers *
+// n_scales isotropic Gaussian kernels with per-sample logits, forward and backward.
+// Compiled twice: -DNFN_FAST=1 and -DNFN_FAST=0.
+//
+//   c_bk   = -0.5 r2_bk / s_k^2 - d log|s_k| - 0.5 d log(2 pi),  r2_bk = sum_j (y_bj - locs_kj)^2
+//   logp_b = logsumexp_k(t_bk + c_bk) - logsumexp_k(t_bk)
+//
+// One streaming pass over the (B, M) logits.  A G-lane group owns a row: lane l holds
+// the logits k = l, l + G, ..., l + (NV - 1) G in registers (coalesced loads), the
+// per-component constants sit in LDS (staged once per workgroup), and the four row
+// reductions (two maxima, two sums) are DPP butterflies inside the group.  Small M packs
+// 64 / G rows into a wave.  Evaluated in the shifted form
+//   m_t = max_k t_k,  a'_k = (t_k - m_t) + c_k,
+//   logp = max a' + log sum exp(a' - max a') - log sum exp(t - m_t),
+// so no term of magnitude |t| is ever subtracted from another.
+#include "nfn_launch.h"
+
+#ifndef NFN_FAST
+#error "compile with -DNFN_FAST=0 or -DNFN_FAST=1"
+#endif
+
+namespace nfn {
+namespace {
+
+constexpr bool kFast = NFN_FAST != 0;
+
+__device__ __forceinline__ float lane_value(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// G = 64: the four 16-lane rows are combined through scalar registers (four v_readlane and
+// three VALU ops; no LDS round trips in the row's dependent chain of four reductions).
+template <int G>
+__device__ __forceinline__ float mix_gsum(float v) {
+  if constexpr (G >= 64) {
+    v = gsum<16>(v);
+    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
+  } else {
+    return gsum<G>(v);
+  }
+}
+
+// Butterfly maximum inside G-lane groups (the DPP steps of gsum).  fmaxf drops a NaN
+// operand: a NaN logit reaches the result through the sums instead.
+template <int G>
+__device__ __forceinline__ float mix_gmax(float v) {
+  if constexpr (G >= 2) v = fmaxf(v, dpp_mov<0xB1>(v));
+  if constexpr (G >= 4) v = fmaxf(v, dpp_mov<0x4E>(v));
+  if constexpr (G >= 8) v = fmaxf(v, dpp_mov<0x141>(v));
+  if constexpr (G >= 16) v = fmaxf(v, dpp_mov<0x140>(v));
+  if constexpr (G == 32) v = fmaxf(v, __shfl_xor(v, 16, 32));
+  if constexpr (G >= 64)
+    v = fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
+  return v;
+}
+
+// Rows a group takes per tile: their loads are issued together (about 8 per lane in flight).
+__host__ __device__ constexpr int mix_rpg(int NV) { return NV >= 8 ? 1 : 8 / NV; }
+
+// LDS: [1 / s_k^2 (M) | -d log|s_k| - 0.5 d log(2 pi) (M) | 1 / s_k (M) | locs transposed (d x M)].
+// The reference's bandwidth can be negative (include/nfn.h): |s| enters the log term only.
+template <int G, int NV, bool FAST, bool GRAD>
+__global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
+  extern __shared__ float lds[];
+  __shared__ double red[2 * kMaxBlock / 64];
+  constexpr int GPB = kMaxBlock / G;  // groups per workgroup
+  constexpr int RPG = mix_rpg(NV);
+  constexpr int ROWS = GPB * RPG;
+  const int M = a.M, d = a.d;
+  const int tid = threadIdx.x;
+  float* inv_s2 = lds;
+  float* lcs = lds + M;
+  float* inv_s = lds + 2 * M;
+  float* locT = lds + 3 * M;
+  for (int k = tid; k < M; k += kMaxBlock) {
+    const double s = (double)a.scales[k];
+    inv_s2[k] = (float)(1.0 / (s * s));
+    lcs[k] = (float)(-(double)d * (log(fabs(s)) + 0.91893853320467274));
+    inv_s[k] = (float)(1.0 / s);
+  }
+  for (int i = tid; i < M * d; i += kMaxBlock) {
+    const int k = i / d, j = i - k * d;
+    locT[j * M + k] = a.locs[i];
+  }
+  __syncthreads();
+  float corr = 0.0f;
+  if (a.y_mean) {
+    for (int j = 0; j < d; ++j) corr += f_log<FAST>(a.y_std[j]);
+  }
+  const int lg = tid & (G - 1), grp = tid / G;
+  // this lane's components: constant over the whole launch
+  int kk[NV];
+  bool act[NV];
+  float is2[NV], lc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int k = lg + G * i;
+    act[i] = k < M;
+    kk[i] = act[i] ? k : 0;
+    is2[i] = inv_s2[kk[i]];
+    lc[i] = lcs[kk[i]];
+  }
+  [[maybe_unused]] float gs[NV];
+  if constexpr (GRAD) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) gs[i] = 0.0f;
+  }
+  double acc = 0.0;
+  int nfc = 0;
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const int64_t b0 = tile * ROWS + grp;
+    float tv[RPG][NV];
+    float y0[RPG];  // the rows' first y value, loaded with the logits (d = 1: all of y)
+    [[maybe_unused]] float g0[RPG];
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) {
+      const int64_t b = b0 + (int64_t)r * GPB;
+      const float* tr = a.logits + b * a.rs;
+      y0[r] = a.y[b < a.B ? b * a.y_bstride : 0];
+      if constexpr (GRAD) g0[r] = b < a.B ? (a.g_out ? a.g_out[b] : 1.0f) : 0.0f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        tv[r][i] = (b < a.B && act[i]) ? __builtin_nontemporal_load(tr + lg + G * i) : -INFINITY;
+    }
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) {
+      const int64_t b = b0 + (int64_t)r * GPB;
+      const bool ok = b < a.B;
+      const float* yr = a.y + (ok ? b * a.y_bstride : 0);
+      float mt = tv[r][0];
+#pragma unroll
+      for (int i = 1; i < NV; ++i) mt = fmaxf(mt, tv[r][i]);
+      mt = mix_gmax<G>(mt);
+      float z2[NV];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) z2[i] = 0.0f;
+      for (int j = 0; j < d; ++j) {
+        float yj = j == 0 ? y0[r] : yr[j];
+        if (a.y_mean) yj = f_div<FAST>(yj - a.y_mean[j], a.y_std[j]);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          const float dy = yj - locT[j * M + kk[i]];
+          z2[i] = fmaf(dy, dy, z2[i]);
+        }
+      }
+      float av[NV], e0[NV], e1[NV];
+      float ma = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        z2[i] *= is2[i];
+        // a lane past M and a -inf logit contribute exactly nothing (no -inf - -inf)
+        const float u = tv[r][i] == -INFINITY ? -INFINITY : tv[r][i] - mt;
+        e0[i] = f_exp<FAST>(u);
+        av[i] = u + fmaf(-0.5f, z2[i], lc[i]);
+        ma = fmaxf(ma, av[i]);
+      }
+      ma = mix_gmax<G>(ma);
+      float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        e1[i] = av[i] == -INFINITY ? 0.0f : f_exp<FAST>(av[i] - ma);
+        s0 += e0[i];
+        s1 += e1[i];
+      }
+      s0 = mix_gsum<G>(s0);
+      s1 = mix_gsum<G>(s1);
+      const float lp = (ma + f_log<FAST>(s1)) - f_log<FAST>(s0) - corr;
+      if (ok && lg == 0) {
+        if (a.out) a.out[b] = lp;
+        acc += (double)lp;
+        nfc += nonfinite1(lp);
+      }
+      if constexpr (GRAD) {
+        const float g = g0[r];
+        const float r0 = f_div<FAST>(1.0f, s0), r1 = f_div<FAST>(1.0f, s1);
+        float post[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          post[i] = e1[i] * r1;
+          if (ok && act[i]) {
+            if (a.grad_logits)
+              __builtin_nontemporal_store(g * (post[i] - e0[i] * r0), a.grad_logits + b * a.gl_rs + lg + G * i);
+            // d/ds_k: post (r2 / s^3 - d / s) = post (z2 - d) / s
+            gs[i] = fmaf(g * post[i], (z2[i] - (float)d) * inv_s[kk[i]], gs[i]);
+          }
+        }
+        if (a.grad_y) {
+          for (int j = 0; j < d; ++j) {
+            float yj = j == 0 ? y0[r] : yr[j];
+            float sd = 1.0f;
+            if (a.y_mean) {
+              sd = a.y_std[j];
+              yj = f_div<FAST>(yj - a.y_mean[j], sd);
+            }
+            float p = 0.0f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) p = fmaf(post[i] * is2[i], locT[j * M + kk[i]] - yj, p);
+            p = mix_gsum<G>(p);
+            if (ok && lg == 0) a.grad_y[b * d + j] = a.y_mean ? f_div<FAST>(g * p, sd) : g * p;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (GRAD) {
+    if (a.part) {
+      // grad_scales: the groups' accumulators summed in group order, one partial row per
+      // workgroup (finished in fixed order by sum_partials_kernel): bitwise deterministic
+      __syncthreads();  // the staged constants are dead
+#pragma unroll
+      for (int i = 0; i < NV; ++i) lds[i * kMaxBlock + tid] = gs[i];
+      __syncthreads();
+      for (int k = tid; k < M; k += kMaxBlock) {
+        const int i = k / G, l = k - i * G;
+        float s = 0.0f;
+        for (int q = 0; q < GPB; ++q) s += lds[i * kMaxBlock + q * G + l];
+        a.part[(int64_t)blockIdx.x * M + k] = s;
+      }
+    }
+  } else {
+    if (a.partials) write_partial(a.partials, acc, nfc, red, a.out_sum, a.epoch);
+  }
+}
+
+template <int G, int NV, bool GRAD>
+int64_t launch_one(const MixArgs& a0, size_t lds, hipStream_t s) {
+  MixArgs a = a0;
+  if (GRAD) lds = std::max(lds, sizeof(float) * NV * kMaxBlock);  // the grad_scales hand-over reuses the LDS
+  constexpr int ROWS = (kMaxBlock / G) * mix_rpg(NV);
+  a.ntiles = (a.B + ROWS - 1) / ROWS;
+  auto kfn = kernel_mixture_kernel<G, NV, kFast, GRAD>;
+  int64_t grid = persistent_grid(kfn, kMaxBlock, lds, a.ntiles);
+  grid = std::max<int64_t>(1, std::min(grid, a.grid_cap));
+  nfn_launch(kfn, dim3((unsigned)grid), dim3(kMaxBlock), (uint32_t)lds, s, a);
+  return grid;
+}
+
+template <bool GRAD>
+int64_t launch_shape(const MixArgs& a, size_t lds, hipStream_t s) {
+  // The row reductions cost the same wave instructions whatever G is, so the narrowest
+  // group whose lanes can hold the row (<= 16 values each) is the cheapest per row: up to
+  // M = 256 a 16-lane group (DPP only, four rows per wave), then 32 and 64 lanes.
+  const int M = a.M;
+  if (M <= 1) return launch_one<1, 1, GRAD>(a, lds, s);
+  if (M <= 2) return launch_one<2, 1, GRAD>(a, lds, s);
+  if (M <= 4) return launch_one<4, 1, GRAD>(a, lds, s);
+  if (M <= 8) return launch_one<8, 1, GRAD>(a, lds, s);
+  if (M <= 16) return launch_one<16, 1, GRAD>(a, lds, s);
+  if (M <= 32) return launch_one<16, 2, GRAD>(a, lds, s);
+  if (M <= 64) return launch_one<16, 4, GRAD>(a, lds, s);
+  if (M <= 128) return launch_one<16, 8, GRAD>(a, lds, s);
+  if (M <= 256) return launch_one<16, 16, GRAD>(a, lds, s);
+  if (M <= 512) return launch_one<32, 16, GRAD>(a, lds, s);
+  if (M <= 1024) return launch_one<64, 16, GRAD>(a, lds, s);
+  return 0;
+}
+
+}  // namespace
+
+#if NFN_FAST
+int64_t launch_mixture_fast(bool grad, const MixArgs& a, size_t lds, hipStream_t s) {
+#else
+int64_t launch_mixture_precise(bool grad, const MixArgs& a, size_t lds, hipStream_t s) {
+#endif
+  return grad ? launch_shape<true>(a, lds, s) : launch_shape<false>(a, lds, s);
+}
+
+}  // namespace nfn

@@ -270,6 +270,18 @@ class InverseNormalizingFlowLayer:
         """Width of ``t``: flow blocks + ``2*n_dims`` for a trainable base."""
         return ops.total_param_size(self._flow_types, self._n_dims, self._trainable_base_dist)
 
+    # --- training hooks (BaseEstimator.fit dispatches through the layer) ---------
+    def trainable_parameters(self, device) -> list:
+        """The layer's own trainable tensors: none (every flow parameter is a column of t)."""
+        return []
+
+    def train_log_prob(self, y, t) -> torch.Tensor:
+        """Differentiable ``log_prob(y | t)`` of a training step (fused forward / backward)."""
+        return ops.log_prob(y, t, self._flow_types, self._n_dims, self._trainable_base_dist)
+
+    def finish_training(self) -> None:
+        pass
+
     @staticmethod
     def _get_bijector(t, flow_types, n_dims):
         """Chain of flows; blocks are split in REVERSED ``flow_types`` order and
@@ -296,3 +308,204 @@ class InverseNormalizingFlowLayer:
     @staticmethod
     def _get_base_dist(t, n_dims, trainable) -> MultivariateNormalDiag:
         return MultivariateNormalDiag(t, n_dims, trainable)
+
+
+# ---------------------------------------------------------------------------
+# Kernel mixture network (estimators/DistributionLayers.py:74-172)
+# ---------------------------------------------------------------------------
+
+def cosine_distances(a: np.ndarray) -> np.ndarray:
+    """Pairwise ``1 - cos(a_i, a_j)`` (scikit-learn's ``cosine_distances``: rows normalised
+    with zero norms left as they are, clipped to [0, 2], exact zeros on the diagonal)."""
+    a = np.asarray(a, np.float64)
+    n = np.linalg.norm(a, axis=1, keepdims=True)
+    n[n == 0.0] = 1.0
+    u = a / n
+    dist = np.clip(1.0 - u @ u.T, 0.0, 2.0)
+    np.fill_diagonal(dist, 0.0)
+    return dist
+
+
+def kmeans_centers(y: np.ndarray, k: int, seed: int = 22, n_iter: int = 100) -> np.ndarray:
+    """``k`` cluster centres of ``y`` (n, d) by a small seeded k-means: k-means++ seeding and
+    Lloyd iterations until the assignment stops changing.  Stands in for the reference's
+    ``sklearn.cluster.KMeans(n_clusters=k).fit(y).cluster_centers_``
+    (``DistributionLayers.py:162-164``); an empty cluster keeps its previous centre."""
+    y = np.asarray(y, np.float64)
+    n = y.shape[0]
+    assert 1 <= k <= n, f"k-means needs 1 <= k <= {n} points, got k = {k}"
+    rng = np.random.default_rng(seed)
+    centers = np.empty((k, y.shape[1]), np.float64)
+    centers[0] = y[rng.integers(n)]
+    d2 = np.sum((y - centers[0]) ** 2, axis=1)
+    for c in range(1, k):
+        tot = d2.sum()
+        idx = int(rng.choice(n, p=d2 / tot)) if tot > 0.0 else int(rng.integers(n))
+        centers[c] = y[idx]
+        d2 = np.minimum(d2, np.sum((y - centers[c]) ** 2, axis=1))
+    assign = None
+    for _ in range(n_iter):
+        dist = ((y[:, None, :] - centers[None, :, :]) ** 2).sum(-1)
+        new = np.argmin(dist, axis=1)
+        if assign is not None and np.array_equal(new, assign):
+            break
+        assign = new
+        for c in range(k):
+            members = y[assign == c]
+            if len(members):
+                centers[c] = members.mean(axis=0)
+    return centers
+
+
+class KernelMixtureDistribution:
+    """``MixtureSameFamily(Categorical(logits=t), MultivariateNormalDiag(locs, scale_identity_
+    multiplier=scales))`` of the reference (``DistributionLayers.py:118-133``), evaluated by
+    the fused mixture kernel (``nfn_kernel_mixture_logprob_f32``)."""
+
+    def __init__(self, t, locs, scales, n_dims: int):
+        self._t = t
+        self._locs = locs
+        self._scales = scales
+        self._n_dims = int(n_dims)
+
+    @property
+    def event_shape(self):
+        return TensorShape([self._n_dims])
+
+    @property
+    def batch_shape(self):
+        return TensorShape(_shape(self._t)[:-1])
+
+    @property
+    def params(self):
+        return self._t
+
+    def log_prob(self, y, y_mean=None, y_std=None):
+        """``log_prob(y)``; optional fused normalisation ``(y-mean)/std`` with the
+        ``-sum(log std)`` correction (``BaseEstimator.py:85-86``)."""
+        M = _shape(self._t)[-1]
+        yy, tt, bshape = _broadcast_rows(y, self._t, self._n_dims, M)
+        if _needs_grad(yy, tt, self._scales):  # training: the fused backward kernel
+            lp = ops.kernel_mixture_log_prob_diff(yy, tt, self._locs, self._scales, y_mean, y_std)
+        else:
+            lp, _ = ops.kernel_mixture_log_prob(yy, tt, self._locs, self._scales, y_mean, y_std)
+        if bshape is not None:
+            return lp.reshape(bshape)
+        if len(self.batch_shape) == 0 and _shape(y) and len(_shape(y)) == 1:
+            return lp.reshape(())
+        return lp
+
+    def prob(self, y, y_mean=None, y_std=None):
+        return torch.exp(self.log_prob(y, y_mean, y_std))
+
+    def log_prob_sum(self, y, y_mean=None, y_std=None, want_nonfinite: bool = False):
+        """``sum_b log_prob(y_b)`` in fp64, reduced on the device (no (B,) output written);
+        with ``want_nonfinite`` also the number of non-finite log-densities."""
+        M = _shape(self._t)[-1]
+        yy, tt, _ = _broadcast_rows(y, self._t, self._n_dims, M)
+        _, s, nf = ops.kernel_mixture_log_prob(yy, tt, self._locs, self._scales, y_mean, y_std,
+                                               want_values=False, want_nonfinite=True)
+        return (s[0], nf[0]) if want_nonfinite else s[0]
+
+    def log_prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
+        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape).
+        One launch per grid row, its ``y`` broadcast over the batch (a plotting path)."""
+        M = _shape(self._t)[-1]
+        t = ops.as_device_f32(self._t)
+        bshape = tuple(t.shape[:-1])
+        t2 = t.reshape(-1, M)
+        yg = ops.as_device_f32(y_grid).reshape(-1, self._n_dims)
+        with torch.no_grad():
+            rows = [ops.kernel_mixture_log_prob(yg[g:g + 1], t2, self._locs, self._scales, y_mean, y_std)[0]
+                    for g in range(yg.shape[0])]
+        return torch.stack(rows).reshape((yg.shape[0],) + bshape)
+
+    def prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
+        return torch.exp(self.log_prob_grid(y_grid, y_mean, y_std))
+
+
+class GaussianKernelsLayer:
+    """Turns a logit tensor ``t (..., n_centers * n_scales)`` into a mixture of Gaussian
+    kernels at fixed centres (``estimators/DistributionLayers.py:74-172``; a Keras
+    ``DistributionLambda`` there, a plain callable here).
+
+    ``locs`` (M, d) is the ``n_centers`` centres repeated per scale (scale 0's block first),
+    zeros until :meth:`set_center_points`; it is not trained.  The bandwidth of scale ``i`` is
+    ``softplus(v[i]) + log(expm1(init_scales[i]))`` with ``v`` a trainable ``(n_scales,)``
+    variable initialised to zeros.
+
+    QUIRK kept from the reference: that formula is not a softplus-inverse parametrisation —
+    at ``v = 0`` and ``init = 0.3`` it is ``0.6931 - 1.0502 = -0.3571``, a NEGATIVE scale.
+    TFP's ``MultivariateNormalDiag`` evaluates it through ``log|s|`` and ``(./s)^2``, so the
+    density is that of ``|s|``; the kernels do the same and the formula is not "fixed"."""
+
+    def __init__(self, n_centers, n_dims, trainable_scale=True, init_scales=(0.3, 0.7)):
+        self.n_centers = int(n_centers)
+        self.n_scales = len(init_scales)
+        self.n_dims = int(n_dims)
+        self.trainable_scale = bool(trainable_scale)
+        self.init_scales = tuple(float(s) for s in init_scales)
+        self._offsets = torch.tensor([float(np.log(np.expm1(s))) for s in self.init_scales], dtype=torch.float32)
+        self.v = torch.zeros((self.n_scales,), dtype=torch.float32)
+        self.locs = np.zeros((self.n_scales * self.n_centers, self.n_dims), np.float32)
+        self._locs_dev = None
+
+    def get_total_param_size(self):
+        return self.n_centers * self.n_scales
+
+    def scales(self, device=None) -> torch.Tensor:
+        """The (M,) bandwidths, differentiable in ``v`` (plain torch ops: the map from
+        ``grad_scales`` to ``v`` — sigmoid, sum over each scale's block — is autograd's)."""
+        dev = self.v.device if device is None else device
+        s = torch.nn.functional.softplus(self.v.to(dev)) + self._offsets.to(dev)
+        return s.repeat_interleave(self.n_centers)
+
+    def _device_locs(self, dev) -> torch.Tensor:
+        if self._locs_dev is None or self._locs_dev.device != dev:
+            self._locs_dev = torch.as_tensor(self.locs, dtype=torch.float32, device=dev).contiguous()
+        return self._locs_dev
+
+    def __call__(self, t) -> KernelMixtureDistribution:
+        assert _shape(t)[-1] == self.n_centers * self.n_scales  # DistributionLayers.py:120
+        dev = ops._device()
+        return KernelMixtureDistribution(t, self._device_locs(dev), self.scales(dev), self.n_dims)
+
+    # --- training hooks (BaseEstimator.fit) -------------------------------------
+    def trainable_parameters(self, device) -> list:
+        """Moves ``v`` to ``device`` as a leaf that requires grad and returns the layer's
+        trainable tensors (none with ``trainable_scale=False``)."""
+        self.v = self.v.detach().to(device).requires_grad_(self.trainable_scale)
+        self._offsets = self._offsets.to(device)
+        return [self.v] if self.trainable_scale else []
+
+    def train_log_prob(self, y, t) -> torch.Tensor:
+        return ops.kernel_mixture_log_prob_diff(y, t, self._device_locs(t.device), self.scales(t.device))
+
+    def finish_training(self) -> None:
+        self.v = self.v.detach()
+
+    def set_center_points(self, y, seed: int = 22):
+        """``DistributionLayers.py:135-172``: ``n_edge = min(2 d, n_centers // 2)`` centres on
+        the data's rim — among the ``2 n_edge`` points farthest from the mean, picked greedily
+        so that the smallest cosine distance to those already picked is largest — the picked
+        points removed from the data, k-means for the other ``n_centers - n_edge`` centres
+        (:func:`kmeans_centers`, seeded), and the centres tiled once per scale."""
+        y = np.asarray(y, np.float64)
+        assert y.ndim == 2 and y.shape[1] == self.n_dims
+        n_edge_points = min(2 * y.shape[1], self.n_centers // 2)
+        parts = []
+        if n_edge_points > 0:
+            farthest_idx = np.argsort(np.linalg.norm(y - y.mean(axis=0), axis=1))[-2 * n_edge_points:]
+            y_farthest = y[farthest_idx]
+            dists = cosine_distances(y_farthest)
+            selected = [0]
+            for _ in range(1, n_edge_points):
+                selected.append(int(np.argsort(np.min(dists[:, selected], axis=1), axis=0)[-1]))
+            parts.append(y_farthest[selected])
+            y = np.delete(y, farthest_idx[selected], axis=0)
+        k = self.n_centers - n_edge_points
+        if k > 0:
+            parts.append(kmeans_centers(y, k, seed=seed))
+        centers = np.concatenate(parts, axis=0)
+        self.locs = np.float32(np.concatenate([centers] * self.n_scales, axis=0))
+        self._locs_dev = None

@@ -12,6 +12,10 @@ base density, the ``-sum(log sigma)`` correction and (for ``score``) the fp64
 batch sum.  ``fit`` trains on the GPU: torch autograd through the MLP and the
 fused backward kernel through the flow chain; the Bayesian
 estimator's variational training (KL term) is not mirrored.
+
+``KernelMixtureNetwork`` (``estimators/KernelMixtureNetwork.py``) shares all of it: ``fit``
+dispatches through the density layer (its trainable tensors, its differentiable train-time
+``log_prob``), so the same loop trains the flow chain or the kernel mixture.
 """
 
 from __future__ import annotations
@@ -22,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .distribution_layers import InverseNormalizingFlowLayer
+from .distribution_layers import GaussianKernelsLayer, InverseNormalizingFlowLayer
 
 _ACTIVATIONS = {
     "tanh": torch.tanh,
@@ -139,6 +143,8 @@ class BaseEstimator:
     def _fused_dense_inputs(self, x):
         """``(h, W, b)`` of the output Dense layer when the fused Dense->chain kernel takes
         the shapes (evaluation only: no autograd through it), else None."""
+        if not isinstance(self.dist_layer, InverseNormalizingFlowLayer):
+            return None  # the fused Dense kernels evaluate a flow chain
         if torch.is_grad_enabled() and any(w.requires_grad for w in (self._mlp.weights if self._mlp else [])):
             return None
         x = ops.as_device_f32(x)
@@ -285,12 +291,17 @@ class BaseEstimator:
         nw = len(self._mlp.weights)
         self._mlp.weights, self._mlp.biases = params[:nw], params[nw:]
         lr = getattr(self, "learning_rate", 3e-3)
+        dl = self.dist_layer
+        # the layer's own trainable tensors (the kernel mixture's bandwidth variable; a flow
+        # layer has none: everything it evaluates comes out of the MLP)
+        layer_params = dl.trainable_parameters(dev)
         # Keras Adam defaults; capturable: the step counts and bias corrections live on the
         # device, so the same optimizer runs eagerly and inside the graph
-        opt = torch.optim.Adam(params, lr=lr, betas=(0.9, 0.999), eps=1e-7, capturable=True)
-        dl = self.dist_layer
-        P = ops.total_param_size(dl.flow_types, self.n_dims, dl.trainable_base_dist)
-        fused_dense = (len(self._mlp.weights) > 1 and self.fused_dense
+        opt = torch.optim.Adam(params + layer_params, lr=lr, betas=(0.9, 0.999), eps=1e-7, capturable=True)
+        P = dl.get_total_param_size()
+        # the output Dense layer can be fused into the flow chain's kernels only
+        fused_dense = (isinstance(dl, InverseNormalizingFlowLayer) and len(self._mlp.weights) > 1
+                       and self.fused_dense
                        and ops.dense_fusable(int(self._mlp.weights[-1].shape[0]), P, self.n_dims))
         batch_size = 32 if batch_size is None else int(batch_size)
         epochs = 1 if epochs is None else int(epochs)
@@ -316,7 +327,7 @@ class BaseEstimator:
                                         dl.flow_types, self.n_dims, dl.trainable_base_dist)
             else:
                 t = self._mlp(xn)
-                lp = ops.log_prob(yc, t, dl.flow_types, self.n_dims, dl.trainable_base_dist)
+                lp = dl.train_log_prob(yc, t)  # the layer's differentiable fused log_prob
             loss = -lp.mean() + sum_log_ys
             loss.backward()
             opt.step()
@@ -385,6 +396,7 @@ class BaseEstimator:
         finally:
             self._mlp.weights = [p.detach() for p in self._mlp.weights]
             self._mlp.biases = [p.detach() for p in self._mlp.biases]
+            dl.finish_training()
         return history
 
 
@@ -409,6 +421,36 @@ class NormalizingFlowNetwork(BaseEstimator):
         return NormalizingFlowNetwork(n_dims=n_dims, n_flows=n_flows, hidden_sizes=hidden_sizes,
                                       trainable_base_dist=trainable_base_dist, noise_reg=noise_reg,
                                       learning_rate=learning_rate, activation=activation)
+
+
+class KernelMixtureNetwork(BaseEstimator):
+    """``estimators/KernelMixtureNetwork.py``: an MLP whose output is the logit row of a
+    mixture of Gaussian kernels at centres fixed from the training targets
+    (``GaussianKernelsLayer``), trained by maximum likelihood together with the layer's
+    bandwidth variable.  ``log_prob`` and its gradient run in the fused mixture kernels
+    (``nfn_kernel_mixture_logprob_f32`` / ``nfn_kernel_mixture_logprob_grad_f32``)."""
+
+    def __init__(self, n_dims, n_centers=50, hidden_sizes=(16, 16), noise_reg=("fixed_rate", 0.0),
+                 learning_rate=3e-3, activation="relu", random_seed=22, n_dims_x=None):
+        dist_layer = GaussianKernelsLayer(n_centers=n_centers, n_dims=n_dims, trainable_scale=True)
+        self.learning_rate = learning_rate
+        super().__init__(dist_layer, n_dims_x=n_dims_x, hidden_sizes=hidden_sizes, activation=activation,
+                         random_seed=random_seed, noise_reg=noise_reg)
+
+    @staticmethod
+    def build_function(n_dims=1, n_centers=30, hidden_sizes=(16, 16), noise_reg=("fixed_rate", 0.0),
+                       learning_rate=2e-3, activation="relu"):
+        return KernelMixtureNetwork(n_dims=n_dims, n_centers=n_centers, hidden_sizes=hidden_sizes,
+                                    noise_reg=noise_reg, learning_rate=learning_rate, activation=activation)
+
+    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, **kwargs):
+        """``KernelMixtureNetwork.py:35-39``: the kernel centres are set from the normalised
+        targets, then the MLP and the bandwidth variable train as in ``BaseEstimator.fit``."""
+        y = np.asarray(y, np.float32)
+        y_mean = np.mean(y, axis=0, dtype=np.float32)
+        y_std = np.std(y, axis=0, dtype=np.float32)
+        self.dist_layer.set_center_points((y - y_mean) / y_std, seed=int(self.random_seed))
+        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)
 
 
 def mean_field_scale(rho: torch.Tensor) -> torch.Tensor:

@@ -1144,3 +1144,131 @@ class DenseGradLauncher:
         rc = self.lib.nfn_chain_logprob_dense_grad_f32(*self._args, stream if stream is not None else _stream())
         if rc != 0:
             _lib.check(rc, "nfn_chain_logprob_dense_grad_f32")
+
+
+# ---------------------------------------------------------------------------
+# Kernel mixture network: Gaussian-kernel mixture log_prob (nfn_mixture.hip)
+# ---------------------------------------------------------------------------
+
+def _mixture_inputs(y, logits, locs, scales, y_mean, y_std, dev):
+    """Device tensors in the C ABI's conventions: ``locs`` (M, d), ``scales`` (M,), ``logits``
+    (B, M) with a unit column stride (a column view of a wider tensor stays a view), ``y``
+    (B or 1, d).  One logit row against a batch of ``y`` is expanded (the ABI's logits rows
+    have a stride >= M)."""
+    locs = as_device_f32(locs, dev)
+    assert locs.dim() == 2, "locs must be (M, n_dims)"
+    locs = locs.contiguous()
+    M, d = int(locs.shape[0]), int(locs.shape[1])
+    scales = as_device_f32(scales, dev).reshape(-1).contiguous()
+    assert scales.numel() == M, f"scales must have {M} elements"
+    y = _prep_2d(y, d, "y", dev)
+    logits = _prep_2d(logits, M, "logits", dev)
+    B = max(int(y.shape[0]), int(logits.shape[0]))
+    assert y.shape[0] in (1, B) and logits.shape[0] in (1, B), "incompatible batch sizes"
+    if logits.shape[0] != B:
+        logits = logits.expand(B, M).contiguous()
+    rs = int(logits.stride(0)) if B > 1 else M
+    if rs < M:  # an expanded (stride-0) batch
+        logits = logits.contiguous()
+        rs = M
+    ym = ys = None
+    if y_mean is not None:
+        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
+        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
+        assert ym.numel() == d and ys.numel() == d
+    return y, logits, rs, locs, scales, ym, ys, B, d, M
+
+
+def kernel_mixture_log_prob(y, logits, locs, scales, y_mean=None, y_std=None, want_values: bool = True,
+                            want_nonfinite: bool = False, want_sum: bool = False):
+    """``log_prob(y)`` of the kernel mixture network's density (``GaussianKernelsLayer``,
+    ``DistributionLayers.py:118-133``) in one fused pass over the logits:
+    ``logsumexp_k(logits + c) - logsumexp_k(logits)`` with ``c_k`` the log-density of kernel
+    ``k`` (centre ``locs[k]``, bandwidth ``scales[k]``, ``|s|`` in the log term only —
+    include/nfn.h).  Returns as :func:`chain_log_prob`: ``(log_prob | None, sum | None)``,
+    plus the non-finite count with ``want_nonfinite``."""
+    dev = _device()
+    y, logits, rs, locs, scales, ym, ys, B, d, M = _mixture_inputs(y, logits, locs, scales, y_mean, y_std, dev)
+    want_sum = want_sum or want_nonfinite or not want_values
+    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
+    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    lib = _lib.load()
+    ws = _workspace(int(lib.nfn_kernel_mixture_workspace_doubles(B, d, M)), dev) if want_sum else None
+    rc = lib.nfn_kernel_mixture_logprob_f32(
+        _ptr(y), _row_stride(y), _ptr(logits), rs, _ptr(locs), _ptr(scales), B, d, M, _ptr(ym), _ptr(ys),
+        _ptr(out), _ptr(osum), _ptr(ws), _stream(),
+    )
+    _lib.check(rc, "nfn_kernel_mixture_logprob_f32")
+    return _with_nonfinite(out, osum, want_nonfinite)
+
+
+def kernel_mixture_log_prob_grad(y, logits, locs, scales, y_mean=None, y_std=None, g_out=None,
+                                 want_logp: bool = False, want_grad_logits: bool = True, want_grad_y: bool = True,
+                                 want_grad_scales: bool = True):
+    """Fused backward of :func:`kernel_mixture_log_prob` for ``L = sum_b g_out[b] * log_prob_b``
+    (``g_out`` None => ones): ``(log_prob | None, dL/dlogits (B, M), dL/dy (B, d), dL/dscales
+    (M,))``.  ``dL/dscales`` is a batch sum: per-workgroup partials and a fixed-order final
+    sum, so the same inputs give the same bits."""
+    dev = _device()
+    y, logits, rs, locs, scales, ym, ys, B, d, M = _mixture_inputs(y, logits, locs, scales, y_mean, y_std, dev)
+    g = None
+    if g_out is not None:
+        g = as_device_f32(g_out, dev).reshape(-1).contiguous()
+        assert g.numel() == B, f"g_out must have {B} elements"
+    lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_logp else None
+    gl = torch.empty((B, M), dtype=torch.float32, device=dev) if want_grad_logits else None
+    gy = torch.empty((B, d), dtype=torch.float32, device=dev) if want_grad_y else None
+    gs = torch.empty((M,), dtype=torch.float32, device=dev) if want_grad_scales else None
+    lib = _lib.load()
+    ws = None
+    if want_grad_scales:  # a float view of the stream's (pinned while capturing) workspace
+        nfl = int(lib.nfn_kernel_mixture_grad_workspace_floats(B, d, M))
+        ws = _workspace((nfl + 1) // 2, dev).view(torch.float32)
+    rc = lib.nfn_kernel_mixture_logprob_grad_f32(
+        _ptr(y), _row_stride(y), _ptr(logits), rs, _ptr(locs), _ptr(scales), B, d, M, _ptr(ym), _ptr(ys), _ptr(g),
+        _ptr(lp), _ptr(gl), M, _ptr(gy), _ptr(gs), _ptr(ws), _stream(),
+    )
+    _lib.check(rc, "nfn_kernel_mixture_logprob_grad_f32")
+    return lp, gl, gy, gs
+
+
+class _KernelMixtureLogProb(torch.autograd.Function):
+    """The mixture ``log_prob`` as a differentiable op: forward and backward are the two fused
+    kernels (nothing but the inputs is saved)."""
+
+    @staticmethod
+    def forward(ctx, y, logits, locs, scales, y_mean, y_std):
+        out, _ = kernel_mixture_log_prob(y, logits, locs, scales, y_mean, y_std)
+        ctx.save_for_backward(y, logits, locs, scales)
+        ctx.meta = (y_mean, y_std)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, logits, locs, scales = ctx.saved_tensors
+        y_mean, y_std = ctx.meta
+        need_y, need_l, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        _, gl, gy, gs = kernel_mixture_log_prob_grad(y, logits, locs, scales, y_mean, y_std, g_out=g.contiguous(),
+                                                     want_grad_logits=need_l, want_grad_y=need_y,
+                                                     want_grad_scales=need_s)
+        B = g.shape[0]
+        if need_y and y.shape[0] == 1 and B > 1:
+            gy = gy.sum(0, keepdim=True)
+        if need_l and logits.shape[0] == 1 and B > 1:
+            gl = gl.sum(0, keepdim=True)
+        return (gy if need_y else None), (gl if need_l else None), None, (gs if need_s else None), None, None
+
+
+def kernel_mixture_log_prob_diff(y, logits, locs, scales, y_mean=None, y_std=None):
+    """Differentiable fused mixture ``log_prob`` (B,): gradients w.r.t. ``logits``, ``scales``
+    and ``y`` come from the fused backward kernel."""
+    dev = _device()
+    locs = as_device_f32(locs, dev).contiguous()
+    M, d = int(locs.shape[0]), int(locs.shape[1])
+    y = _prep_2d(y, d, "y", dev)
+    logits = _prep_2d(logits, M, "logits", dev)
+    scales = as_device_f32(scales, dev).reshape(-1)
+    if y_mean is not None:
+        y_mean = as_device_f32(y_mean, dev).reshape(-1).contiguous()
+        y_std = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    return _KernelMixtureLogProb.apply(y, logits, locs, scales, y_mean, y_std)

@@ -87,6 +87,25 @@ int main() {
   EXPECT(nfn_split_blocks_f32(f, 8, 0, w3, 3, f, nullptr), NFN_OK);
   EXPECT(nfn_chain_logprob_grid_f32(nullptr, 1, 4, nullptr, 8, 10, 1, pr, 2, 1, nullptr, nullptr, nullptr, 10, nullptr), NFN_E_NULLPTR);
   EXPECT(nfn_chain_logprob_grid_f32(nullptr, 1, -1, nullptr, 8, 10, 1, pr, 2, 1, nullptr, nullptr, nullptr, 10, nullptr), NFN_E_SHAPE);
+  // kernel mixture: forward and backward rejection paths, workspace sizes
+  for (int64_t B : {(int64_t)0, (int64_t)1, (int64_t)1000, (int64_t)1 << 24, (int64_t)1 << 27}) {
+    EXPECT(nfn_kernel_mixture_workspace_doubles(B, 1, 100) >= 0, 1);
+    EXPECT(nfn_kernel_mixture_grad_workspace_floats(B, 1, 100) >= 0, 1);
+  }
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 100, f, f, 10, 1, 0, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 1025, f, f, 10, 1, 1025, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 100, f, f, 10, 0, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 32, f, 1024, f, f, 10, 32, 1024, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 99, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 100, f, f, -1, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 100, f, f, 10, 1, 100, f, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_kernel_mixture_logprob_f32(nullptr, 1, f, 100, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 100, nullptr, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_kernel_mixture_logprob_f32(f, 1, f, 100, f, f, 10, 1, 100, nullptr, nullptr, f, dd, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, f, 10, 1, 1025, nullptr, nullptr, nullptr, nullptr, f, 1025, f, f, f, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, f, 10, 1, 100, nullptr, nullptr, nullptr, nullptr, f, 99, f, f, f, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, nullptr, 10, 1, 100, nullptr, nullptr, nullptr, nullptr, f, 100, f, f, f, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, f, 10, 1, 100, nullptr, nullptr, nullptr, nullptr, f, 100, f, f, nullptr, nullptr), NFN_E_NULLPTR);
   // communicator
   void* comm = nullptr;
   uint8_t uid[NFN_COMM_ID_BYTES];
