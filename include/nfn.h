@@ -103,7 +103,7 @@ extern "C" {
 /* Library version as MAJOR*10000 + MINOR*100 + PATCH.
  *   203 (0.2.3): + nfn_set_launch_events (additive, measurement hook); later also, with
  *                no version change (additive, every earlier entry unchanged), the four
- *                nfn_kernel_mixture_* entries.
+ *                nfn_kernel_mixture_* entries and the three nfn_gaussian_mixture_* entries.
  *   202 (0.2.2): + nfn_flow_vjp_f32 (additive).
  *   201 (0.2.1): + nfn_split_blocks_f32 (additive; every 200 entry point unchanged).
  *   200 (0.2.0): out_sum is a device double[2] {sum, non-finite count} (was double[1]);
@@ -392,6 +392,45 @@ int32_t nfn_kernel_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, c
                                             const float* g_out, float* out_logp, float* grad_logits,
                                             int64_t grad_logits_rowstride, float* grad_y, float* grad_scales,
                                             float* workspace, void* stream);
+
+/*
+ * Mixture density network density (GaussianMixtureLayer, estimators/DistributionLayers.py:174-212):
+ * tfd.Mixture(Categorical(logits), K x MultivariateNormalDiag), every parameter taken from the
+ * per-sample row t of width P = K * (2*d + 1):
+ *   t[2*k*d : 2*k*d + d]         loc_k           (component k = 0 .. K-1)
+ *   t[2*k*d + d : 2*k*d + 2*d]   raw_k
+ *   t[2*K*d : 2*K*d + K]         the K logits l
+ *   sigma_kj    = softplus(0.05 * raw_kj + log(expm1(1)))
+ *   z_kj        = (y_j - loc_kj) / sigma_kj
+ *   c_k         = -0.5 * sum_j z_kj^2 - sum_j log sigma_kj - 0.5*d*log(2*pi)
+ *   out_logp[b] = logsumexp_k(l_k + c_k) - logsumexp_k(l_k)  [- sum_j log y_std_j]
+ * (y_b replaced by (y_b - y_mean) / y_std when given; both or neither).
+ *   y        : (B or 1, d) rows at y_bstride floats (0 = broadcast)
+ *   t        : (B, P) rows at t_rowstride floats (>= P: a column view of a wider tensor works)
+ *   out_logp (nullable), out_sum (nullable), workspace : as for nfn_chain_logprob_f32, with
+ *              workspace a device double[nfn_gaussian_mixture_workspace_doubles(B, d, K)]
+ * A -inf logit removes its component: it contributes exact zeros to every output.  A row whose
+ * logits are all -inf, any +inf logit and any NaN in the row give a non-finite out_logp, which
+ * out_sum[1] counts.  There is no floor under sigma (the reference has none).
+ * Limits: K >= 1, 1 <= d <= NFN_MAX_DIMS, K * (2*d + 1) <= 1023, B >= 0 (else NFN_E_SHAPE).
+ *
+ * Backward, for L = sum_b g_out[b] * out_logp[b] (g_out NULL = ones), with
+ * post = softmax_k(l + c), prior = softmax_k(l), x_kj = 0.05 * raw_kj + log(expm1(1)):
+ *   dL/dl_k    = g * (post_k - prior_k)
+ *   dL/dloc_kj = g * post_k * z_kj / sigma_kj
+ *   dL/draw_kj = g * post_k * (z_kj^2 - 1) / sigma_kj * 0.05 * sigmoid(x_kj)
+ *   dL/dy_j    = -g * sum_k post_k * z_kj / sigma_kj  [/ y_std_j]
+ * grad_t (B, P) at grad_t_rowstride >= P holds the first three in t's layout; grad_y is (B, d)
+ * contiguous.  Every output is nullable.  No batch-reduced output, so no workspace.
+ */
+int64_t nfn_gaussian_mixture_workspace_doubles(int64_t B, int32_t d, int32_t K);
+int32_t nfn_gaussian_mixture_logprob_f32(const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride,
+                                         int64_t B, int32_t d, int32_t K, const float* y_mean, const float* y_std,
+                                         float* out_logp, double* out_sum, double* workspace, void* stream);
+int32_t nfn_gaussian_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride,
+                                              int64_t B, int32_t d, int32_t K, const float* y_mean,
+                                              const float* y_std, const float* g_out, float* out_logp, float* grad_t,
+                                              int64_t grad_t_rowstride, float* grad_y, void* stream);
 
 /*
  * Multi-GPU (one process per GPU, batch sharded over ranks).  The communicator

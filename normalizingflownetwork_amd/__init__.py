@@ -6,6 +6,7 @@ Layout:
                          nfn_persistent / nfn_group / nfn_tile (forward, posterior),
                          nfn_grad (fused backward), nfn_misc (reductions),
                          nfn_mixture (kernel mixture log_prob, forward + backward),
+                         nfn_gmm (mixture density network log_prob, forward + backward),
                          nfn_comm (RCCL all-reduce), nfn_api (validation + dispatch)
   build.py               parallel hipcc build of libnfn_hip.so (in-tree)
   _lib.py                ctypes binding of libnfn_hip.so (no CPU fallback)
@@ -19,9 +20,11 @@ Layout:
   parallel.py            batch-sharded multi-GPU mean log-likelihood (RCCL all-reduce)
 """
 
-from .distribution_layers import (FlowDistribution, GaussianKernelsLayer, InverseNormalizingFlowLayer,
-                                  KernelMixtureDistribution, TensorShape)
-from .estimators import BayesNormalizingFlowNetwork, KernelMixtureNetwork, NormalizingFlowNetwork
+from .distribution_layers import (FlowDistribution, GaussianKernelsLayer, GaussianMixtureDistribution,
+                                  GaussianMixtureLayer, InverseNormalizingFlowLayer, KernelMixtureDistribution,
+                                  TensorShape)
+from .estimators import (BayesNormalizingFlowNetwork, KernelMixtureNetwork, MixtureDensityNetwork,
+                         NormalizingFlowNetwork)
 from .normalizing_flows import FLOWS, AffineFlow, Bijector, Chain, Invert, PlanarFlow, RadialFlow
 
 __version__ = "0.1.0"
@@ -42,4 +45,7 @@ __all__ = [
     "GaussianKernelsLayer",
     "KernelMixtureDistribution",
     "KernelMixtureNetwork",
+    "GaussianMixtureLayer",
+    "GaussianMixtureDistribution",
+    "MixtureDensityNetwork",
 ]

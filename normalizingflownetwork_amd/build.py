@@ -51,6 +51,8 @@ UNITS = [
     ("dense_grad", "nfn_dense_grad.hip", []),
     ("mixture_fast", "nfn_mixture.hip", ["-DNFN_FAST=1"]),
     ("mixture_precise", "nfn_mixture.hip", ["-DNFN_FAST=0"]),
+    ("gmm_fast", "nfn_gmm.hip", ["-DNFN_FAST=1"]),
+    ("gmm_precise", "nfn_gmm.hip", ["-DNFN_FAST=0"]),
     ("sample", "nfn_sample.hip", []),
     ("comm", "nfn_comm.hip", []),
 ]

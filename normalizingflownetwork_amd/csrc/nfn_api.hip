@@ -879,6 +879,63 @@ int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* l
   return rc;
 }
 
+// Gaussian mixture of the mixture density network (nfn_gmm.hip).  A wave tile holds at
+// least 16 rows and the persistent grid never exceeds kGmmMaxParts workgroups: ONE function
+// sizes the workspace and caps every launch.
+constexpr int64_t kGmmMaxParts = 2048;
+int64_t gmm_parts(int64_t B) { return std::max<int64_t>(1, std::min<int64_t>(kGmmMaxParts, (B + 15) / 16)); }
+
+int32_t run_gmm(bool grad, const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride, int64_t B,
+                int32_t d, int32_t K, const float* y_mean, const float* y_std, const float* g_out, float* out_logp,
+                double* out_sum, double* workspace, float* grad_t, int64_t grad_t_rowstride, float* grad_y,
+                void* stream) {
+  g_last_error.clear();
+  const HookScope hook_scope;
+  if (K < 1) return fail(NFN_E_SHAPE, "number of components K must be >= 1");
+  if (d < 1 || d > NFN_MAX_DIMS) return fail(NFN_E_SHAPE, "n_dims out of range");
+  const int64_t P = (int64_t)K * (2 * d + 1);
+  if (P > 1023) return fail(NFN_E_SHAPE, "row width K * (2 * n_dims + 1) must be <= 1023");
+  if (B < 0) return fail(NFN_E_SHAPE, "batch size must be >= 0");
+  if (y_bstride < 0 || (y_bstride != 0 && y_bstride < d)) return fail(NFN_E_SHAPE, "bad y batch stride");
+  if (t_rowstride < P) return fail(NFN_E_SHAPE, "t row stride < K * (2 * n_dims + 1)");
+  if (grad && grad_t && grad_t_rowstride < P) return fail(NFN_E_SHAPE, "grad_t row stride < K * (2 * n_dims + 1)");
+  if ((y_mean == nullptr) != (y_std == nullptr)) return fail(NFN_E_NULLPTR, "y_mean and y_std must both be given or both NULL");
+  if (!y || !t) return fail(NFN_E_NULLPTR, "y or t is NULL");
+  if (out_sum && !workspace) return fail(NFN_E_NULLPTR, "workspace is NULL but out_sum requested");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (B == 0) {
+    if (out_sum && hipMemsetAsync(out_sum, 0, 2 * sizeof(double), s) != hipSuccess) return check_hip("hipMemsetAsync");
+    return NFN_OK;
+  }
+  GmmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.y = y;
+  a.t = t;
+  a.y_mean = y_mean;
+  a.y_std = y_std;
+  a.g_out = g_out;
+  a.out = out_logp;
+  a.y_bstride = y_bstride;
+  a.rs = t_rowstride;
+  a.B = B;
+  a.d = d;
+  a.K = K;
+  a.P = (int32_t)P;
+  a.grid_cap = gmm_parts(B);
+  if (grad) {
+    a.grad_t = grad_t;
+    a.gt_rs = grad_t ? grad_t_rowstride : 0;
+    a.grad_y = grad_y;
+  } else if (workspace) {
+    a.partials = workspace + 2;
+    a.out_sum = out_sum;
+    a.epoch = out_sum ? next_epoch() : 0u;
+  }
+  const int64_t grid = use_fast_math() ? launch_gmm_fast(grad, a, s) : launch_gmm_precise(grad, a, s);
+  if (grid <= 0) return fail(NFN_E_SHAPE, "no Gaussian mixture launch for this shape");
+  return check_hip("gaussian_mixture_kernel launch");
+}
+
 }  // namespace
 }  // namespace nfn
 
@@ -1021,6 +1078,28 @@ int32_t nfn_kernel_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, c
   return run_mixture(true, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std, g_out,
                      out_logp, nullptr, nullptr, grad_logits, grad_logits_rowstride, grad_y, grad_scales, workspace,
                      stream);
+}
+
+int64_t nfn_gaussian_mixture_workspace_doubles(int64_t B, int32_t d, int32_t K) {
+  (void)d;
+  (void)K;
+  if (B <= 0) return 0;
+  return 2 + 2 * gmm_parts(B);  // [count | ticket | (sum, count) pairs]
+}
+
+int32_t nfn_gaussian_mixture_logprob_f32(const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride,
+                                         int64_t B, int32_t d, int32_t K, const float* y_mean, const float* y_std,
+                                         float* out_logp, double* out_sum, double* workspace, void* stream) {
+  return run_gmm(false, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, nullptr, out_logp, out_sum, workspace,
+                 nullptr, 0, nullptr, stream);
+}
+
+int32_t nfn_gaussian_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride,
+                                              int64_t B, int32_t d, int32_t K, const float* y_mean,
+                                              const float* y_std, const float* g_out, float* out_logp, float* grad_t,
+                                              int64_t grad_t_rowstride, float* grad_y, void* stream) {
+  return run_gmm(true, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, g_out, out_logp, nullptr, nullptr,
+                 grad_t, grad_t_rowstride, grad_y, stream);
 }
 
 int32_t nfn_posterior_lse_dense_f32(const float* y, int64_t y_bstride, const float* h, int64_t h_drawstride,

@@ -235,6 +235,38 @@ struct MixArgs {
 // launches the (G, NV) instance for M; returns the grid (= number of partials written)
 int64_t launch_mixture_fast(bool grad, const MixArgs& a, size_t lds, hipStream_t s);
 int64_t launch_mixture_precise(bool grad, const MixArgs& a, size_t lds, hipStream_t s);
+// nfn_gmm.hip (compiled once per math mode): the mixture density network's Gaussian-mixture
+// log_prob (nfn_gaussian_mixture_logprob_f32) and its backward
+struct GmmArgs {
+  const float* y;        // (B or 1, d) rows at y_bstride floats
+  const float* t;        // (B, P) rows at rs floats, P = K (2 d + 1)
+  const float* y_mean;   // (d,) or NULL
+  const float* y_std;
+  const float* g_out;    // backward: upstream gradient (B,) or NULL = ones
+  float* out;            // (B,) log_prob, or NULL
+  double* partials;      // forward: the workspace's (sum, count) pairs, or NULL
+  double* out_sum;
+  float* grad_t;         // (B, P) rows at gt_rs floats, or NULL
+  float* grad_y;         // (B, d) contiguous, or NULL
+  int64_t y_bstride;
+  int64_t rs;
+  int64_t gt_rs;
+  int64_t B;
+  int64_t ntiles;        // set by the launcher: tiles of R rows
+  int64_t grid_cap;      // the workspace's partial slots
+  int32_t d;
+  int32_t K;
+  int32_t P;
+  int32_t S;             // set by the launcher: LDS row stride of t, P | 1
+  int32_t Sy;            // set by the launcher: LDS row stride of y, d | 1
+  int32_t R;             // set by the launcher: rows per wave tile (64, 32 or 16)
+  int32_t vec4;          // set by the launcher: t rows can be streamed as float4
+  int32_t gt_vec4;       // set by the launcher: grad_t rows can be written as float4
+  uint32_t epoch;
+};
+// returns the grid (= number of partials written); 0 if the shape has no launch
+int64_t launch_gmm_fast(bool grad, const GmmArgs& a, hipStream_t s);
+int64_t launch_gmm_precise(bool grad, const GmmArgs& a, hipStream_t s);
 // nfn_sample.hip
 void launch_sample(bool fast, int dm, const SampleArgs& sa, dim3 grid, dim3 block, size_t lds, hipStream_t s);
 // nfn_grid.hip

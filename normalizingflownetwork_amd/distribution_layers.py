@@ -509,3 +509,104 @@ class GaussianKernelsLayer:
         centers = np.concatenate(parts, axis=0)
         self.locs = np.float32(np.concatenate([centers] * self.n_scales, axis=0))
         self._locs_dev = None
+
+
+# ---------------------------------------------------------------------------
+# Mixture density network (estimators/DistributionLayers.py:174-212)
+# ---------------------------------------------------------------------------
+
+class GaussianMixtureDistribution:
+    """``Mixture(Categorical(logits), K x MultivariateNormalDiag(loc_k, softplus(0.05 raw_k +
+    log(expm1(1)))))`` of the reference (``DistributionLayers.py:196-212``), every parameter
+    read from the row ``t``, evaluated by the fused Gaussian-mixture kernel
+    (``nfn_gaussian_mixture_logprob_f32``)."""
+
+    def __init__(self, t, n_centers: int, n_dims: int):
+        self._t = t
+        self._n_centers = int(n_centers)
+        self._n_dims = int(n_dims)
+
+    @property
+    def event_shape(self):
+        return TensorShape([self._n_dims])
+
+    @property
+    def batch_shape(self):
+        return TensorShape(_shape(self._t)[:-1])
+
+    @property
+    def params(self):
+        return self._t
+
+    def log_prob(self, y, y_mean=None, y_std=None):
+        """``log_prob(y)``; optional fused normalisation ``(y-mean)/std`` with the
+        ``-sum(log std)`` correction (``BaseEstimator.py:85-86``)."""
+        P = _shape(self._t)[-1]
+        yy, tt, bshape = _broadcast_rows(y, self._t, self._n_dims, P)
+        if _needs_grad(yy, tt):  # training: the fused backward kernel
+            lp = ops.gaussian_mixture_log_prob_diff(yy, tt, self._n_centers, self._n_dims, y_mean, y_std)
+        else:
+            lp, _ = ops.gaussian_mixture_log_prob(yy, tt, self._n_centers, self._n_dims, y_mean, y_std)
+        if bshape is not None:
+            return lp.reshape(bshape)
+        if len(self.batch_shape) == 0 and _shape(y) and len(_shape(y)) == 1:
+            return lp.reshape(())
+        return lp
+
+    def prob(self, y, y_mean=None, y_std=None):
+        return torch.exp(self.log_prob(y, y_mean, y_std))
+
+    def log_prob_sum(self, y, y_mean=None, y_std=None, want_nonfinite: bool = False):
+        """``sum_b log_prob(y_b)`` in fp64, reduced on the device (no (B,) output written);
+        with ``want_nonfinite`` also the number of non-finite log-densities."""
+        P = _shape(self._t)[-1]
+        yy, tt, _ = _broadcast_rows(y, self._t, self._n_dims, P)
+        _, s, nf = ops.gaussian_mixture_log_prob(yy, tt, self._n_centers, self._n_dims, y_mean, y_std,
+                                                 want_values=False, want_nonfinite=True)
+        return (s[0], nf[0]) if want_nonfinite else s[0]
+
+    def log_prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
+        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape).
+        One launch per grid row, its ``y`` broadcast over the batch (a plotting path)."""
+        P = _shape(self._t)[-1]
+        t = ops.as_device_f32(self._t)
+        bshape = tuple(t.shape[:-1])
+        t2 = t.reshape(-1, P)
+        yg = ops.as_device_f32(y_grid).reshape(-1, self._n_dims)
+        with torch.no_grad():
+            rows = [ops.gaussian_mixture_log_prob(yg[g:g + 1], t2, self._n_centers, self._n_dims, y_mean, y_std)[0]
+                    for g in range(yg.shape[0])]
+        return torch.stack(rows).reshape((yg.shape[0],) + bshape)
+
+    def prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
+        return torch.exp(self.log_prob_grid(y_grid, y_mean, y_std))
+
+
+class GaussianMixtureLayer:
+    """Turns a parameter tensor ``t (..., n_centers * (2 * n_dims + 1))`` into a mixture of
+    ``n_centers`` diagonal Gaussians whose locations, scales and mixture weights all come from
+    ``t`` (``estimators/DistributionLayers.py:174-212``; a Keras ``DistributionLambda`` there,
+    a plain callable here).  Row layout: ``[loc_0 | raw_0 | ... | loc_{K-1} | raw_{K-1} |
+    logits]``.  The layer has no parameters of its own."""
+
+    def __init__(self, n_centers, n_dims):
+        self.n_centers = int(n_centers)
+        self.n_dims = int(n_dims)
+
+    def get_total_param_size(self):
+        return self.n_centers + 2 * self.n_dims * self.n_centers
+
+    def __call__(self, t) -> GaussianMixtureDistribution:
+        # the reference's slices would give components of the wrong event size (a shape error)
+        assert _shape(t)[-1] == self.get_total_param_size()
+        return GaussianMixtureDistribution(t, self.n_centers, self.n_dims)
+
+    # --- training hooks (BaseEstimator.fit) -------------------------------------
+    def trainable_parameters(self, device) -> list:
+        return []
+
+    def train_log_prob(self, y, t) -> torch.Tensor:
+        return ops.gaussian_mixture_log_prob_diff(y, t, self.n_centers, self.n_dims)
+
+    def finish_training(self) -> None:
+        pass

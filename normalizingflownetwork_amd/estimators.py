@@ -16,6 +16,7 @@ estimator's variational training (KL term) is not mirrored.
 ``KernelMixtureNetwork`` (``estimators/KernelMixtureNetwork.py``) shares all of it: ``fit``
 dispatches through the density layer (its trainable tensors, its differentiable train-time
 ``log_prob``), so the same loop trains the flow chain or the kernel mixture.
+``MixtureDensityNetwork`` (``estimators/MixtureDensityNetwork.py``) is the third such layer.
 """
 
 from __future__ import annotations
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .distribution_layers import GaussianKernelsLayer, InverseNormalizingFlowLayer
+from .distribution_layers import GaussianKernelsLayer, GaussianMixtureLayer, InverseNormalizingFlowLayer
 
 _ACTIVATIONS = {
     "tanh": torch.tanh,
@@ -451,6 +452,27 @@ class KernelMixtureNetwork(BaseEstimator):
         y_std = np.std(y, axis=0, dtype=np.float32)
         self.dist_layer.set_center_points((y - y_mean) / y_std, seed=int(self.random_seed))
         return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)
+
+
+class MixtureDensityNetwork(BaseEstimator):
+    """``estimators/MixtureDensityNetwork.py``: an MLP whose output row holds the locations,
+    scales and mixture logits of ``n_centers`` diagonal Gaussians (``GaussianMixtureLayer``),
+    trained by maximum likelihood.  ``log_prob`` and its gradient run in the fused
+    Gaussian-mixture kernels (``nfn_gaussian_mixture_logprob_f32`` /
+    ``nfn_gaussian_mixture_logprob_grad_f32``)."""
+
+    def __init__(self, n_dims, n_centers, hidden_sizes=(16, 16), noise_reg=("fixed_rate", 0.0),
+                 learning_rate=3e-3, activation="relu", random_seed=22, n_dims_x=None):
+        dist_layer = GaussianMixtureLayer(n_centers=n_centers, n_dims=n_dims)
+        self.learning_rate = learning_rate
+        super().__init__(dist_layer, n_dims_x=n_dims_x, hidden_sizes=hidden_sizes, activation=activation,
+                         random_seed=random_seed, noise_reg=noise_reg)
+
+    @staticmethod
+    def build_function(n_dims=1, n_centers=5, hidden_sizes=(16, 16), noise_reg=("fixed_rate", 0.0),
+                       learning_rate=2e-3, activation="relu"):
+        return MixtureDensityNetwork(n_dims=n_dims, n_centers=n_centers, hidden_sizes=hidden_sizes,
+                                     noise_reg=noise_reg, learning_rate=learning_rate, activation=activation)
 
 
 def mean_field_scale(rho: torch.Tensor) -> torch.Tensor:

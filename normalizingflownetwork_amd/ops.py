@@ -1272,3 +1272,113 @@ def kernel_mixture_log_prob_diff(y, logits, locs, scales, y_mean=None, y_std=Non
         y_mean = as_device_f32(y_mean, dev).reshape(-1).contiguous()
         y_std = as_device_f32(y_std, dev).reshape(-1).contiguous()
     return _KernelMixtureLogProb.apply(y, logits, locs, scales, y_mean, y_std)
+
+
+# ---------------------------------------------------------------------------
+# Mixture density network: Gaussian-mixture log_prob (nfn_gmm.hip)
+# ---------------------------------------------------------------------------
+
+def _gmm_inputs(y, t, n_centers, n_dims, y_mean, y_std, dev):
+    """Device tensors in the C ABI's conventions: ``t`` (B, P = K (2 d + 1)) with a unit
+    column stride (a column view of a wider tensor stays a view), ``y`` (B or 1, d).  One
+    parameter row against a batch of ``y`` is expanded (the ABI's rows have a stride >= P)."""
+    K, d = int(n_centers), int(n_dims)
+    P = K * (2 * d + 1)
+    y = _prep_2d(y, d, "y", dev)
+    t = _prep_2d(t, P, "t", dev)
+    B = max(int(y.shape[0]), int(t.shape[0]))
+    assert y.shape[0] in (1, B) and t.shape[0] in (1, B), "incompatible batch sizes"
+    if t.shape[0] != B:
+        t = t.expand(B, P).contiguous()
+    rs = int(t.stride(0)) if B > 1 else P
+    if rs < P:  # an expanded (stride-0) batch
+        t = t.contiguous()
+        rs = P
+    ym = ys = None
+    if y_mean is not None:
+        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
+        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
+        assert ym.numel() == d and ys.numel() == d
+    return y, t, rs, ym, ys, B, d, K, P
+
+
+def gaussian_mixture_log_prob(y, t, n_centers, n_dims, y_mean=None, y_std=None, want_values: bool = True,
+                              want_nonfinite: bool = False, want_sum: bool = False):
+    """``log_prob(y)`` of the mixture density network's density (``GaussianMixtureLayer``,
+    ``DistributionLayers.py:174-212``) in one fused pass over the parameter rows ``t``
+    ``[loc_0 | raw_0 | ... | loc_{K-1} | raw_{K-1} | logits]`` (include/nfn.h).  Returns as
+    :func:`chain_log_prob`: ``(log_prob | None, sum | None)``, plus the non-finite count with
+    ``want_nonfinite``."""
+    dev = _device()
+    y, t, rs, ym, ys, B, d, K, _ = _gmm_inputs(y, t, n_centers, n_dims, y_mean, y_std, dev)
+    want_sum = want_sum or want_nonfinite or not want_values
+    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
+    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    lib = _lib.load()
+    ws = _workspace(int(lib.nfn_gaussian_mixture_workspace_doubles(B, d, K)), dev) if want_sum else None
+    rc = lib.nfn_gaussian_mixture_logprob_f32(
+        _ptr(y), _row_stride(y), _ptr(t), rs, B, d, K, _ptr(ym), _ptr(ys), _ptr(out), _ptr(osum), _ptr(ws),
+        _stream(),
+    )
+    _lib.check(rc, "nfn_gaussian_mixture_logprob_f32")
+    return _with_nonfinite(out, osum, want_nonfinite)
+
+
+def gaussian_mixture_log_prob_grad(y, t, n_centers, n_dims, y_mean=None, y_std=None, g_out=None,
+                                   want_logp: bool = False, want_grad_t: bool = True, want_grad_y: bool = True):
+    """Fused backward of :func:`gaussian_mixture_log_prob` for ``L = sum_b g_out[b] *
+    log_prob_b`` (``g_out`` None => ones): ``(log_prob | None, dL/dt (B, P), dL/dy (B, d))``."""
+    dev = _device()
+    y, t, rs, ym, ys, B, d, K, P = _gmm_inputs(y, t, n_centers, n_dims, y_mean, y_std, dev)
+    g = None
+    if g_out is not None:
+        g = as_device_f32(g_out, dev).reshape(-1).contiguous()
+        assert g.numel() == B, f"g_out must have {B} elements"
+    lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_logp else None
+    gt = torch.empty((B, P), dtype=torch.float32, device=dev) if want_grad_t else None
+    gy = torch.empty((B, d), dtype=torch.float32, device=dev) if want_grad_y else None
+    rc = _lib.load().nfn_gaussian_mixture_logprob_grad_f32(
+        _ptr(y), _row_stride(y), _ptr(t), rs, B, d, K, _ptr(ym), _ptr(ys), _ptr(g), _ptr(lp), _ptr(gt), P,
+        _ptr(gy), _stream(),
+    )
+    _lib.check(rc, "nfn_gaussian_mixture_logprob_grad_f32")
+    return lp, gt, gy
+
+
+class _GaussianMixtureLogProb(torch.autograd.Function):
+    """The Gaussian-mixture ``log_prob`` as a differentiable op: forward and backward are the
+    two fused kernels (nothing but the inputs is saved)."""
+
+    @staticmethod
+    def forward(ctx, y, t, n_centers, n_dims, y_mean, y_std):
+        out, _ = gaussian_mixture_log_prob(y, t, n_centers, n_dims, y_mean, y_std)
+        ctx.save_for_backward(y, t)
+        ctx.meta = (n_centers, n_dims, y_mean, y_std)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, t = ctx.saved_tensors
+        n_centers, n_dims, y_mean, y_std = ctx.meta
+        need_y, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        _, gt, gy = gaussian_mixture_log_prob_grad(y, t, n_centers, n_dims, y_mean, y_std, g_out=g.contiguous(),
+                                                   want_grad_t=need_t, want_grad_y=need_y)
+        B = g.shape[0]
+        if need_y and y.shape[0] == 1 and B > 1:
+            gy = gy.sum(0, keepdim=True)
+        if need_t and t.shape[0] == 1 and B > 1:
+            gt = gt.sum(0, keepdim=True)
+        return (gy if need_y else None), (gt if need_t else None), None, None, None, None
+
+
+def gaussian_mixture_log_prob_diff(y, t, n_centers, n_dims, y_mean=None, y_std=None):
+    """Differentiable fused Gaussian-mixture ``log_prob`` (B,): gradients w.r.t. ``t`` and
+    ``y`` come from the fused backward kernel."""
+    dev = _device()
+    K, d = int(n_centers), int(n_dims)
+    y = _prep_2d(y, d, "y", dev)
+    t = _prep_2d(t, K * (2 * d + 1), "t", dev)
+    if y_mean is not None:
+        y_mean = as_device_f32(y_mean, dev).reshape(-1).contiguous()
+        y_std = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    return _GaussianMixtureLogProb.apply(y, t, K, d, y_mean, y_std)

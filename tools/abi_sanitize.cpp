@@ -106,6 +106,27 @@ int main() {
   EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, f, 10, 1, 100, nullptr, nullptr, nullptr, nullptr, f, 99, f, f, f, nullptr), NFN_E_SHAPE);
   EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, nullptr, 10, 1, 100, nullptr, nullptr, nullptr, nullptr, f, 100, f, f, f, nullptr), NFN_E_NULLPTR);
   EXPECT(nfn_kernel_mixture_logprob_grad_f32(f, 1, f, 100, f, f, 10, 1, 100, nullptr, nullptr, nullptr, nullptr, f, 100, f, f, nullptr, nullptr), NFN_E_NULLPTR);
+  // Gaussian mixture (mixture density network): rejection paths, workspace sizes, B = 0
+  for (int64_t B : {(int64_t)0, (int64_t)1, (int64_t)1000, (int64_t)1 << 24, (int64_t)1 << 27})
+    EXPECT(nfn_gaussian_mixture_workspace_doubles(B, 1, 5) >= 0, 1);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 15, 10, 1, 0, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 15, 10, 0, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 33, f, 335, 10, 33, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 1026, 10, 1, 342, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 32, f, big, 10, 32, 1 << 30, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 14, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 15, -1, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 2, f, 35, 10, 3, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 15, 10, 1, 5, f, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(nullptr, 1, f, 15, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, nullptr, 15, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 15, 10, 1, 5, nullptr, nullptr, f, dd, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_gaussian_mixture_logprob_f32(f, 1, f, 1023, 0, 1, 341, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_OK);
+  EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, f, 1026, 10, 1, 342, nullptr, nullptr, nullptr, nullptr, f, 1026, f, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, f, 15, 10, 1, 5, nullptr, nullptr, nullptr, nullptr, f, 14, f, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, nullptr, 15, 10, 1, 5, nullptr, nullptr, nullptr, nullptr, f, 15, f, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, f, 15, 10, 1, 5, nullptr, f, nullptr, nullptr, f, 15, f, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, f, 15, 0, 1, 5, nullptr, nullptr, nullptr, nullptr, f, 15, f, nullptr), NFN_OK);
   // communicator
   void* comm = nullptr;
   uint8_t uid[NFN_COMM_ID_BYTES];
