@@ -114,15 +114,93 @@ class MultivariateNormalDiag:
         return torch.exp(self.log_prob(x))
 
 
-class FlowDistribution:
+class _RowDensity:
+    """A conditional density whose parameters are the rows of ``t (..., width)``, evaluated by
+    fused kernels over 2-D rows.  A subclass supplies ``_forward`` (its forward op, no
+    autograd), ``_diff`` (its differentiable op) and, beyond ``t``, the tensors that may
+    require grad (``_grad_inputs``)."""
+
+    def __init__(self, t, n_dims: int):
+        self._t = t
+        self._n_dims = int(n_dims)
+
+    def _forward(self, y, t, y_mean, y_std, **want):
+        """The forward op on rows: ``(log_prob | None, sum | None[, non-finite count])``."""
+        raise NotImplementedError
+
+    def _diff(self, y, t, y_mean, y_std) -> torch.Tensor:
+        """The differentiable op on rows: ``log_prob`` (B,) with the fused backward behind it."""
+        raise NotImplementedError
+
+    def _grad_inputs(self) -> tuple:
+        return ()
+
+    @property
+    def _width(self) -> int:
+        return _shape(self._t)[-1]
+
+    @property
+    def event_shape(self):
+        return TensorShape([self._n_dims])
+
+    @property
+    def batch_shape(self):
+        return TensorShape(_shape(self._t)[:-1])
+
+    @property
+    def params(self):
+        return self._t
+
+    def log_prob(self, y, y_mean=None, y_std=None):
+        """``log_prob(y)``; optional fused normalisation ``(y-mean)/std`` with the
+        ``-sum(log std)`` Jacobian correction (``BaseEstimator.py:85-86``)."""
+        yy, tt, bshape = _broadcast_rows(y, self._t, self._n_dims, self._width)
+        if _needs_grad(yy, tt, *self._grad_inputs()):  # training: the fused backward kernel
+            lp = self._diff(yy, tt, y_mean, y_std)
+        else:
+            lp, _ = self._forward(yy, tt, y_mean, y_std)
+        if bshape is not None:
+            return lp.reshape(bshape)
+        if len(self.batch_shape) == 0 and _shape(y) and len(_shape(y)) == 1:
+            return lp.reshape(())
+        return lp
+
+    def prob(self, y, y_mean=None, y_std=None):
+        return torch.exp(self.log_prob(y, y_mean, y_std))
+
+    def log_prob_sum(self, y, y_mean=None, y_std=None, want_nonfinite: bool = False):
+        """``sum_b log_prob(y_b)`` in fp64, reduced on the device (no (B,) output written);
+        with ``want_nonfinite`` also the number of non-finite log-densities (fp64 scalar)."""
+        yy, tt, _ = _broadcast_rows(y, self._t, self._n_dims, self._width)
+        _, s, nf = self._forward(yy, tt, y_mean, y_std, want_values=False, want_nonfinite=True)
+        return (s[0], nf[0]) if want_nonfinite else s[0]
+
+    def _grid_rows(self, y_grid):
+        """``(y_grid (G, d), t (B, width), batch shape)`` of a density grid."""
+        t = ops.as_device_f32(self._t)
+        t2 = t if t.dim() == 2 else t.reshape(-1, self._width)
+        return ops.as_device_f32(y_grid).reshape(-1, self._n_dims), t2, tuple(t.shape[:-1])
+
+    def log_prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
+        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape).
+        One launch per grid row, its ``y`` broadcast over the batch (a plotting path)."""
+        yg, t2, bshape = self._grid_rows(y_grid)
+        with torch.no_grad():
+            rows = [self._forward(yg[g:g + 1], t2, y_mean, y_std)[0] for g in range(yg.shape[0])]
+        return torch.stack(rows).reshape((yg.shape[0],) + bshape)
+
+    def prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
+        return torch.exp(self.log_prob_grid(y_grid, y_mean, y_std))
+
+
+class FlowDistribution(_RowDensity):
     """``TransformedDistribution(base, Invert(Chain(...)))`` of the reference,
     evaluated by the fused kernel."""
 
     def __init__(self, t, n_dims: int, flow_types: Sequence[str], trainable_base_dist: bool):
-        self._n_dims = int(n_dims)
+        super().__init__(t, n_dims)
         self._flow_types = tuple(flow_types)
         self._trainable = bool(trainable_base_dist)
-        self._t = t
         self.distribution = InverseNormalizingFlowLayer._get_base_dist(t, n_dims, trainable_base_dist)
         # A wrong width raises AssertionError at construction, as in the reference
         # (DistributionLayers.py:272); the Chain itself (and the parameter snapshot its flows
@@ -149,57 +227,18 @@ class FlowDistribution:
                 self._bijector = Invert(InverseNormalizingFlowLayer._get_bijector(flow_t, self._flow_types, d))
         return self._bijector
 
-    @property
-    def event_shape(self):
-        return TensorShape([self._n_dims])
+    def _forward(self, y, t, y_mean, y_std, **want):
+        return ops.chain_log_prob(y, t, self._flow_types, self._n_dims, self._trainable, y_mean, y_std, **want)
 
-    @property
-    def batch_shape(self):
-        return TensorShape(_shape(self._t)[:-1])
-
-    @property
-    def params(self):
-        return self._t
-
-    def log_prob(self, y, y_mean=None, y_std=None):
-        """``log_prob(y)``; optional fused normalisation ``(y-mean)/std`` with the
-        ``-sum(log std)`` Jacobian correction (``BaseEstimator.py:85-86``)."""
-        P = _shape(self._t)[-1]
-        yy, tt, bshape = _broadcast_rows(y, self._t, self._n_dims, P)
-        if _needs_grad(yy, tt):  # training: differentiable through the fused backward kernel
-            lp = ops.log_prob(yy, tt, self._flow_types, self._n_dims, self._trainable, y_mean, y_std)
-        else:
-            lp, _ = ops.chain_log_prob(yy, tt, self._flow_types, self._n_dims, self._trainable, y_mean, y_std)
-        if bshape is not None:
-            return lp.reshape(bshape)
-        if len(self.batch_shape) == 0 and _shape(y) and len(_shape(y)) == 1:
-            return lp.reshape(())
-        return lp
-
-    def log_prob_sum(self, y, y_mean=None, y_std=None, want_nonfinite: bool = False):
-        """``sum_b log_prob(y_b)`` in fp64, reduced on the device (no (B,) output written);
-        with ``want_nonfinite`` also the number of non-finite log-densities (fp64 scalar)."""
-        P = _shape(self._t)[-1]
-        yy, tt, _ = _broadcast_rows(y, self._t, self._n_dims, P)
-        _, s, nf = ops.chain_log_prob(yy, tt, self._flow_types, self._n_dims, self._trainable, y_mean, y_std,
-                                      want_values=False, want_nonfinite=True)
-        return (s[0], nf[0]) if want_nonfinite else s[0]
-
-    def prob(self, y, y_mean=None, y_std=None):
-        return torch.exp(self.log_prob(y, y_mean, y_std))
+    def _diff(self, y, t, y_mean, y_std):
+        return ops.log_prob(y, t, self._flow_types, self._n_dims, self._trainable, y_mean, y_std)
 
     def log_prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
-        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape)."""
-        P = _shape(self._t)[-1]
-        t = ops.as_device_f32(self._t)
-        bshape = tuple(t.shape[:-1])
-        t2 = t.reshape(-1, P) if t.dim() != 2 else t
-        yg = ops.as_device_f32(y_grid).reshape(-1, self._n_dims)
+        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape),
+        by the grid kernel (one launch)."""
+        yg, t2, bshape = self._grid_rows(y_grid)
         out = ops.chain_log_prob_grid(yg, t2, self._flow_types, self._n_dims, self._trainable, y_mean, y_std)
         return out.reshape((yg.shape[0],) + bshape)
-
-    def prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
-        return torch.exp(self.log_prob_grid(y_grid, y_mean, y_std))
 
     def sample(self, sample_shape=(), seed=None) -> torch.Tensor:
         """Draws of shape ``sample_shape + batch_shape + [d]`` through the inverted flows
@@ -357,71 +396,24 @@ def kmeans_centers(y: np.ndarray, k: int, seed: int = 22, n_iter: int = 100) -> 
     return centers
 
 
-class KernelMixtureDistribution:
+class KernelMixtureDistribution(_RowDensity):
     """``MixtureSameFamily(Categorical(logits=t), MultivariateNormalDiag(locs, scale_identity_
     multiplier=scales))`` of the reference (``DistributionLayers.py:118-133``), evaluated by
     the fused mixture kernel (``nfn_kernel_mixture_logprob_f32``)."""
 
     def __init__(self, t, locs, scales, n_dims: int):
-        self._t = t
+        super().__init__(t, n_dims)
         self._locs = locs
         self._scales = scales
-        self._n_dims = int(n_dims)
 
-    @property
-    def event_shape(self):
-        return TensorShape([self._n_dims])
+    def _forward(self, y, t, y_mean, y_std, **want):
+        return ops.kernel_mixture_log_prob(y, t, self._locs, self._scales, y_mean, y_std, **want)
 
-    @property
-    def batch_shape(self):
-        return TensorShape(_shape(self._t)[:-1])
+    def _diff(self, y, t, y_mean, y_std):
+        return ops.kernel_mixture_log_prob_diff(y, t, self._locs, self._scales, y_mean, y_std)
 
-    @property
-    def params(self):
-        return self._t
-
-    def log_prob(self, y, y_mean=None, y_std=None):
-        """``log_prob(y)``; optional fused normalisation ``(y-mean)/std`` with the
-        ``-sum(log std)`` correction (``BaseEstimator.py:85-86``)."""
-        M = _shape(self._t)[-1]
-        yy, tt, bshape = _broadcast_rows(y, self._t, self._n_dims, M)
-        if _needs_grad(yy, tt, self._scales):  # training: the fused backward kernel
-            lp = ops.kernel_mixture_log_prob_diff(yy, tt, self._locs, self._scales, y_mean, y_std)
-        else:
-            lp, _ = ops.kernel_mixture_log_prob(yy, tt, self._locs, self._scales, y_mean, y_std)
-        if bshape is not None:
-            return lp.reshape(bshape)
-        if len(self.batch_shape) == 0 and _shape(y) and len(_shape(y)) == 1:
-            return lp.reshape(())
-        return lp
-
-    def prob(self, y, y_mean=None, y_std=None):
-        return torch.exp(self.log_prob(y, y_mean, y_std))
-
-    def log_prob_sum(self, y, y_mean=None, y_std=None, want_nonfinite: bool = False):
-        """``sum_b log_prob(y_b)`` in fp64, reduced on the device (no (B,) output written);
-        with ``want_nonfinite`` also the number of non-finite log-densities."""
-        M = _shape(self._t)[-1]
-        yy, tt, _ = _broadcast_rows(y, self._t, self._n_dims, M)
-        _, s, nf = ops.kernel_mixture_log_prob(yy, tt, self._locs, self._scales, y_mean, y_std,
-                                               want_values=False, want_nonfinite=True)
-        return (s[0], nf[0]) if want_nonfinite else s[0]
-
-    def log_prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
-        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape).
-        One launch per grid row, its ``y`` broadcast over the batch (a plotting path)."""
-        M = _shape(self._t)[-1]
-        t = ops.as_device_f32(self._t)
-        bshape = tuple(t.shape[:-1])
-        t2 = t.reshape(-1, M)
-        yg = ops.as_device_f32(y_grid).reshape(-1, self._n_dims)
-        with torch.no_grad():
-            rows = [ops.kernel_mixture_log_prob(yg[g:g + 1], t2, self._locs, self._scales, y_mean, y_std)[0]
-                    for g in range(yg.shape[0])]
-        return torch.stack(rows).reshape((yg.shape[0],) + bshape)
-
-    def prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
-        return torch.exp(self.log_prob_grid(y_grid, y_mean, y_std))
+    def _grad_inputs(self) -> tuple:
+        return (self._scales,)
 
 
 class GaussianKernelsLayer:
@@ -515,71 +507,21 @@ class GaussianKernelsLayer:
 # Mixture density network (estimators/DistributionLayers.py:174-212)
 # ---------------------------------------------------------------------------
 
-class GaussianMixtureDistribution:
+class GaussianMixtureDistribution(_RowDensity):
     """``Mixture(Categorical(logits), K x MultivariateNormalDiag(loc_k, softplus(0.05 raw_k +
     log(expm1(1)))))`` of the reference (``DistributionLayers.py:196-212``), every parameter
     read from the row ``t``, evaluated by the fused Gaussian-mixture kernel
     (``nfn_gaussian_mixture_logprob_f32``)."""
 
     def __init__(self, t, n_centers: int, n_dims: int):
-        self._t = t
+        super().__init__(t, n_dims)
         self._n_centers = int(n_centers)
-        self._n_dims = int(n_dims)
 
-    @property
-    def event_shape(self):
-        return TensorShape([self._n_dims])
+    def _forward(self, y, t, y_mean, y_std, **want):
+        return ops.gaussian_mixture_log_prob(y, t, self._n_centers, self._n_dims, y_mean, y_std, **want)
 
-    @property
-    def batch_shape(self):
-        return TensorShape(_shape(self._t)[:-1])
-
-    @property
-    def params(self):
-        return self._t
-
-    def log_prob(self, y, y_mean=None, y_std=None):
-        """``log_prob(y)``; optional fused normalisation ``(y-mean)/std`` with the
-        ``-sum(log std)`` correction (``BaseEstimator.py:85-86``)."""
-        P = _shape(self._t)[-1]
-        yy, tt, bshape = _broadcast_rows(y, self._t, self._n_dims, P)
-        if _needs_grad(yy, tt):  # training: the fused backward kernel
-            lp = ops.gaussian_mixture_log_prob_diff(yy, tt, self._n_centers, self._n_dims, y_mean, y_std)
-        else:
-            lp, _ = ops.gaussian_mixture_log_prob(yy, tt, self._n_centers, self._n_dims, y_mean, y_std)
-        if bshape is not None:
-            return lp.reshape(bshape)
-        if len(self.batch_shape) == 0 and _shape(y) and len(_shape(y)) == 1:
-            return lp.reshape(())
-        return lp
-
-    def prob(self, y, y_mean=None, y_std=None):
-        return torch.exp(self.log_prob(y, y_mean, y_std))
-
-    def log_prob_sum(self, y, y_mean=None, y_std=None, want_nonfinite: bool = False):
-        """``sum_b log_prob(y_b)`` in fp64, reduced on the device (no (B,) output written);
-        with ``want_nonfinite`` also the number of non-finite log-densities."""
-        P = _shape(self._t)[-1]
-        yy, tt, _ = _broadcast_rows(y, self._t, self._n_dims, P)
-        _, s, nf = ops.gaussian_mixture_log_prob(yy, tt, self._n_centers, self._n_dims, y_mean, y_std,
-                                                 want_values=False, want_nonfinite=True)
-        return (s[0], nf[0]) if want_nonfinite else s[0]
-
-    def log_prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
-        """``log_prob`` of each grid value (G, d) under every batch member: (G, *batch_shape).
-        One launch per grid row, its ``y`` broadcast over the batch (a plotting path)."""
-        P = _shape(self._t)[-1]
-        t = ops.as_device_f32(self._t)
-        bshape = tuple(t.shape[:-1])
-        t2 = t.reshape(-1, P)
-        yg = ops.as_device_f32(y_grid).reshape(-1, self._n_dims)
-        with torch.no_grad():
-            rows = [ops.gaussian_mixture_log_prob(yg[g:g + 1], t2, self._n_centers, self._n_dims, y_mean, y_std)[0]
-                    for g in range(yg.shape[0])]
-        return torch.stack(rows).reshape((yg.shape[0],) + bshape)
-
-    def prob_grid(self, y_grid, y_mean=None, y_std=None) -> torch.Tensor:
-        return torch.exp(self.log_prob_grid(y_grid, y_mean, y_std))
+    def _diff(self, y, t, y_mean, y_std):
+        return ops.gaussian_mixture_log_prob_diff(y, t, self._n_centers, self._n_dims, y_mean, y_std)
 
 
 class GaussianMixtureLayer:

@@ -69,6 +69,17 @@ def total_param_size(flow_types: Sequence[str], n_dims: int, trainable_base: boo
     return sum(param_size(f, n_dims) for f in flow_types) + (2 * n_dims if trainable_base else 0)
 
 
+def flow_block_offsets(flow_types: Sequence[str], n_dims: int, trainable_base: bool) -> list:
+    """Column of each row of ``t`` where flow k's block starts, in the layer's reversed layout
+    (``_get_bijector``, ``DistributionLayers.py:267-278``): the base's ``2 n_dims`` columns when
+    trainable, then the blocks of the LAST flow type first."""
+    off, offs = 2 * int(n_dims) if trainable_base else 0, [0] * len(flow_types)
+    for k in reversed(range(len(flow_types))):
+        offs[k] = off
+        off += param_size(flow_types[k], n_dims)
+    return offs
+
+
 _workspaces: "collections.OrderedDict" = collections.OrderedDict()
 _ws_lock = threading.Lock()
 # (device, stream) workspaces kept at once; the least recently used is dropped beyond
@@ -162,6 +173,79 @@ def _prep_2d(x, width: int, name: str, device) -> torch.Tensor:
     return x
 
 
+def _norm_stats(y_mean, y_std, n_dims: int, device):
+    """``y_mean`` / ``y_std`` as (n_dims,) device arrays, or ``(None, None)``.  The kernels
+    read ``n_dims`` floats of each, so every entry point checks the lengths here."""
+    if y_mean is None:
+        return None, None
+    ym = as_device_f32(y_mean, device).reshape(-1).contiguous()
+    ys = as_device_f32(y_std, device).reshape(-1).contiguous()
+    assert ym.numel() == n_dims and ys.numel() == n_dims, f"y_mean and y_std must have {n_dims} elements"
+    return ym, ys
+
+
+def _upstream(g_out, B: int, device) -> Optional[torch.Tensor]:
+    """The upstream gradient ``g_out`` as a (B,) device array (None => ones in the kernel)."""
+    if g_out is None:
+        return None
+    g = as_device_f32(g_out, device).reshape(-1).contiguous()
+    assert g.numel() == B, f"g_out must have {B} elements"
+    return g
+
+
+def _param_rows(t, P: int, device):
+    """``(t, row stride, rows)`` of the chain's parameter rows ``t`` (B or 1, P); an empty
+    chain over a fixed base (P = 0) reads nothing and gets one dummy row."""
+    if P == 0:
+        return torch.zeros((1, 1), dtype=torch.float32, device=device), 0, 1
+    t = _prep_2d(t, P, "t", device)
+    return t, _row_stride(t), int(t.shape[0])
+
+
+def _chain_inputs(y, t, flow_types: Sequence[str], n_dims: int, trainable_base: bool, device, name: str = "y"):
+    """``(y, t, t_stride, B, P)`` of a chain entry: ``y`` (B or 1, d) against ``t`` (B or 1, P)."""
+    P = total_param_size(flow_types, n_dims, trainable_base)
+    y = _prep_2d(y, n_dims, name, device)
+    t, t_stride, rows = _param_rows(t, P, device)
+    B = max(int(y.shape[0]), rows)
+    assert y.shape[0] in (1, B) and rows in (1, B), "incompatible batch sizes"
+    return y, t, t_stride, B, P
+
+
+def _row_inputs(y, rows, width: int, n_dims: int, y_mean, y_std, device, name: str):
+    """``(y, rows, row stride, y_mean, y_std, B)`` of a mixture entry: ``rows`` (B, width) with a
+    unit column stride (a column view of a wider tensor stays a view), ``y`` (B or 1, d).  The
+    ABI's rows have a stride >= width, so a single row against a batch of ``y`` and an expanded
+    (stride-0) batch are materialised."""
+    y = _prep_2d(y, n_dims, "y", device)
+    rows = _prep_2d(rows, width, name, device)
+    B = max(int(y.shape[0]), int(rows.shape[0]))
+    assert y.shape[0] in (1, B) and rows.shape[0] in (1, B), "incompatible batch sizes"
+    if rows.shape[0] != B:
+        rows = rows.expand(B, width).contiguous()
+    stride = int(rows.stride(0)) if B > 1 else width
+    if stride < width:
+        rows, stride = rows.contiguous(), width
+    return (y, rows, stride) + _norm_stats(y_mean, y_std, n_dims, device) + (B,)
+
+
+def _sum_outputs(B: int, want_values: bool, want_sum: bool, workspace_doubles, device, workspace: bool = False):
+    """``(out (B,) | None, out_sum (2,) fp64 | None, workspace | None)`` of a summing entry.
+    ``workspace_doubles()`` sizes the stream's workspace, taken with ``want_sum`` (or always,
+    with ``workspace``)."""
+    out = torch.empty((B,), dtype=torch.float32, device=device) if want_values else None
+    osum = torch.empty((2,), dtype=torch.float64, device=device) if want_sum else None
+    ws = _workspace(int(workspace_doubles()), device) if (want_sum or workspace) else None
+    return out, osum, ws
+
+
+def _unbroadcast(grad: Optional[torch.Tensor], x: torch.Tensor, B: int) -> Optional[torch.Tensor]:
+    """The per-sample gradient rows summed for an input that was one row broadcast over B."""
+    if grad is not None and x.shape[0] == 1 and B > 1:
+        return grad.sum(0, keepdim=True)
+    return grad
+
+
 def chain_log_prob(
     y,
     t,
@@ -182,24 +266,14 @@ def chain_log_prob(
     ``log_prob((y-mu)/sigma) - sum(log sigma)`` (``BaseEstimator.py:77-86``).
     """
     dev = _device()
-    P = total_param_size(flow_types, n_dims, trainable_base)
-    y = _prep_2d(y, n_dims, "y", dev)
-    t = _prep_2d(t, P, "t", dev) if P > 0 else torch.zeros((1, 1), dtype=torch.float32, device=dev)
-    B = max(y.shape[0], t.shape[0] if P > 0 else 1)
-    assert y.shape[0] in (1, B) and (P == 0 or t.shape[0] in (1, B)), "incompatible batch sizes"
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-        assert ym.numel() == n_dims and ys.numel() == n_dims
-    want_sum = want_sum or want_nonfinite
-    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
-    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    y, t, t_stride, B, P = _chain_inputs(y, t, flow_types, n_dims, trainable_base, dev)
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
     lib = _lib.load()
-    ws = _workspace(int(lib.nfn_chain_workspace_doubles(B, n_dims, P)), dev) if want_sum else None
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite,
+                                 lambda: lib.nfn_chain_workspace_doubles(B, n_dims, P), dev)
     ids, k = flow_ids(flow_types)
     rc = lib.nfn_chain_logprob_f32(
-        _ptr(y), _row_stride(y), _ptr(t), _row_stride(t) if P > 0 else 0, B, int(n_dims),
+        _ptr(y), _row_stride(y), _ptr(t), t_stride, B, int(n_dims),
         ctypes.cast(ids, ctypes.c_void_p), k, int(bool(trainable_base)), _ptr(ym), _ptr(ys),
         _ptr(out), _ptr(osum), _ptr(ws), _stream(),
     )
@@ -227,26 +301,15 @@ def chain_log_prob_grad(
     (``BaseEstimator.py:19-31, 55-59``).  A broadcast input (batch 1) still gets
     one gradient row per sample.  Returns ``(log_prob | None, grad_t | None, grad_y | None)``."""
     dev = _device()
-    P = total_param_size(flow_types, n_dims, trainable_base)
-    y = _prep_2d(y, n_dims, "y", dev)
-    t = _prep_2d(t, P, "t", dev) if P > 0 else torch.zeros((1, 1), dtype=torch.float32, device=dev)
-    B = max(y.shape[0], t.shape[0] if P > 0 else 1)
-    assert y.shape[0] in (1, B) and (P == 0 or t.shape[0] in (1, B)), "incompatible batch sizes"
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-        assert ym.numel() == n_dims and ys.numel() == n_dims
-    g = None
-    if g_out is not None:
-        g = as_device_f32(g_out, dev).reshape(-1).contiguous()
-        assert g.numel() == B, f"g_out must have {B} elements"
+    y, t, t_stride, B, P = _chain_inputs(y, t, flow_types, n_dims, trainable_base, dev)
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
+    g = _upstream(g_out, B, dev)
     lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_logp else None
     gt = torch.empty((B, P), dtype=torch.float32, device=dev) if (want_grad_t and P > 0) else None
     gy = torch.empty((B, n_dims), dtype=torch.float32, device=dev) if want_grad_y else None
     ids, k = flow_ids(flow_types)
     rc = _lib.load().nfn_chain_logprob_grad_f32(
-        _ptr(y), _row_stride(y), _ptr(t), _row_stride(t) if P > 0 else 0, B, int(n_dims),
+        _ptr(y), _row_stride(y), _ptr(t), t_stride, B, int(n_dims),
         ctypes.cast(ids, ctypes.c_void_p), k, int(bool(trainable_base)), _ptr(ym), _ptr(ys), _ptr(g),
         _ptr(lp), _ptr(gt), P if gt is not None else 0, _ptr(gy), _stream(),
     )
@@ -276,23 +339,15 @@ class _ChainLogProb(torch.autograd.Function):
         _, gt, gy = chain_log_prob_grad(y, t, flow_types, n_dims, trainable_base, y_mean, y_std,
                                         g_out=g.contiguous(), want_grad_t=need_t, want_grad_y=need_y)
         B = g.shape[0]
-        if need_y and y.shape[0] == 1 and B > 1:
-            gy = gy.sum(0, keepdim=True)
-        if need_t and t.shape[0] == 1 and B > 1:
-            gt = gt.sum(0, keepdim=True)
-        return (gy if need_y else None), (gt if need_t else None), None, None, None, None, None
+        return _unbroadcast(gy, y, B), _unbroadcast(gt, t, B), None, None, None, None, None
 
 
 def log_prob(y, t, flow_types: Sequence[str], n_dims: int, trainable_base: bool, y_mean=None, y_std=None):
     """Differentiable fused ``log_prob`` (B,): gradients w.r.t. ``t`` and ``y`` flow
     through ``torch.autograd`` via the fused backward kernel."""
     dev = _device()
-    P = total_param_size(flow_types, n_dims, trainable_base)
-    y = _prep_2d(y, n_dims, "y", dev)
-    t = _prep_2d(t, P, "t", dev) if P > 0 else torch.zeros((1, 1), dtype=torch.float32, device=dev)
-    if y_mean is not None:
-        y_mean = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        y_std = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    y, t, _, _, _ = _chain_inputs(y, t, flow_types, n_dims, trainable_base, dev)
+    y_mean, y_std = _norm_stats(y_mean, y_std, n_dims, dev)
     return _ChainLogProb.apply(y, t, tuple(flow_types), int(n_dims), bool(trainable_base), y_mean, y_std)
 
 
@@ -314,9 +369,7 @@ class _DenseLogProb(torch.autograd.Function):
         flow_types, n_dims, trainable_base = ctx.meta
         _, gh, gW, gb, gy = chain_log_prob_dense_grad(y, h, W, b, flow_types, n_dims, trainable_base,
                                                       g_out=g.contiguous())
-        if y.shape[0] == 1 and gh.shape[0] > 1:
-            gy = gy.sum(0, keepdim=True)
-        return gy, gh, gW, gb, None, None, None
+        return _unbroadcast(gy, y, gh.shape[0]), gh, gW, gb, None, None, None
 
 
 def log_prob_dense(y, h, W, b, flow_types: Sequence[str], n_dims: int, trainable_base: bool):
@@ -335,6 +388,19 @@ DENSE_HIDDEN_WIDTHS = (4, 8, 16, 32, 64)
 def dense_fusable(H: int, P: int, n_dims: int) -> bool:
     """Shapes the fused Dense->chain kernel takes (include/nfn.h, nfn_chain_logprob_dense_f32)."""
     return H in DENSE_HIDDEN_WIDTHS and 1 <= P <= 64 and n_dims <= 8
+
+
+def _dense_inputs(h, W, b, P: int, n_dims: int, device):
+    """``(h, W, b, B, H, fused)`` of the output Dense layer ``h`` (B, H), ``W`` (H, P), ``b`` (P,)
+    or None; ``fused`` says whether the fused kernels take the shape and ``h``'s alignment."""
+    h = as_device_f32(h, device)
+    assert h.dim() == 2, "h must be (B, H)"
+    B, H = int(h.shape[0]), int(h.shape[1])
+    W = as_device_f32(W, device).contiguous()
+    assert tuple(W.shape) == (H, P), f"W must be ({H}, {P})"
+    bb = None if b is None else as_device_f32(b, device).reshape(-1).contiguous()
+    fused = dense_fusable(H, P, n_dims) and h.stride(0) % 4 == 0 and h.data_ptr() % 16 == 0
+    return h, W, bb, B, H, fused
 
 
 def chain_log_prob_dense(
@@ -357,28 +423,17 @@ def chain_log_prob_dense(
     as a library GEMM (torch) followed by the chain kernel."""
     dev = _device()
     P = total_param_size(flow_types, n_dims, trainable_base)
-    h = as_device_f32(h, dev)
-    assert h.dim() == 2, "h must be (B, H)"
-    H = int(h.shape[1])
-    W = as_device_f32(W, dev).contiguous()
-    assert tuple(W.shape) == (H, P), f"W must be ({H}, {P})"
-    bb = None if b is None else as_device_f32(b, dev).reshape(-1).contiguous()
-    if not dense_fusable(H, P, n_dims) or h.stride(0) % 4 or h.data_ptr() % 16:
+    h, W, bb, B, H, fused = _dense_inputs(h, W, b, P, n_dims, dev)
+    if not fused:
         t = h @ W + (bb if bb is not None else 0.0)
         return chain_log_prob(y, t, flow_types, n_dims, trainable_base, y_mean, y_std, want_values, want_sum,
                               want_nonfinite)
     y = _prep_2d(y, n_dims, "y", dev)
-    B = int(h.shape[0])
     assert y.shape[0] in (1, B), "incompatible batch sizes"
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-    want_sum = want_sum or want_nonfinite
-    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
-    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
     lib = _lib.load()
-    ws = _workspace(int(lib.nfn_chain_workspace_doubles(B, n_dims, P)), dev) if want_sum else None
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite,
+                                 lambda: lib.nfn_chain_workspace_doubles(B, n_dims, P), dev)
     ids, k = flow_ids(flow_types)
     rc = lib.nfn_chain_logprob_dense_f32(
         _ptr(y), _row_stride(y), _ptr(h), int(h.stride(0)), H, _ptr(W), _ptr(bb), B, int(n_dims),
@@ -411,25 +466,13 @@ def chain_log_prob_dense_grad(
     :func:`chain_log_prob_grad`."""
     dev = _device()
     P = total_param_size(flow_types, n_dims, trainable_base)
-    h = as_device_f32(h, dev)
-    assert h.dim() == 2, "h must be (B, H)"
-    B, H = int(h.shape[0]), int(h.shape[1])
-    W = as_device_f32(W, dev).contiguous()
-    assert tuple(W.shape) == (H, P), f"W must be ({H}, {P})"
-    bb = None if b is None else as_device_f32(b, dev).reshape(-1).contiguous()
+    h, W, bb, B, H, fused = _dense_inputs(h, W, b, P, n_dims, dev)
     y = _prep_2d(y, n_dims, "y", dev)
     assert y.shape[0] in (1, B), "incompatible batch sizes"
-    g = None
-    if g_out is not None:
-        g = as_device_f32(g_out, dev).reshape(-1).contiguous()
-        assert g.numel() == B, f"g_out must have {B} elements"
+    g = _upstream(g_out, B, dev)
     lib = _lib.load()
-    rc = _lib.NFN_E_SHAPE
-    if dense_fusable(H, P, n_dims) and h.stride(0) % 4 == 0 and h.data_ptr() % 16 == 0:
-        ym = ys = None
-        if y_mean is not None:
-            ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-            ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    if fused:
+        ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
         lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_logp else None
         gh = torch.empty((B, H), dtype=torch.float32, device=dev)
         gW = torch.empty((H, P), dtype=torch.float32, device=dev)
@@ -498,15 +541,10 @@ def posterior_lse_dense(
                              want_nonfinite)
     y = _prep_2d(y, n_dims, "y", dev)
     assert y.shape[0] in (1, B), "incompatible batch sizes"
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-    want_sum = want_sum or want_nonfinite
-    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
-    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
     lib = _lib.load()
-    ws = _workspace(int(lib.nfn_chain_workspace_doubles(B, n_dims, P)), dev) if want_sum else None
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite,
+                                 lambda: lib.nfn_chain_workspace_doubles(B, n_dims, P), dev)
     ids, k = flow_ids(flow_types)
     rc = lib.nfn_posterior_lse_dense_f32(
         _ptr(y), _row_stride(y), _ptr(h), hdraw, hrow, H, _ptr(W), H * P, _ptr(bb), P, S, B, int(n_dims),
@@ -517,98 +555,19 @@ def posterior_lse_dense(
     return _with_nonfinite(out, osum, want_nonfinite)
 
 
-class DenseLauncher:
-    """Pre-bound fused Dense->chain launch over fixed device buffers (benchmark loop)."""
-
-    def __init__(self, y: torch.Tensor, h: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor],
-                 flow_types: Sequence[str], n_dims: int, trainable_base: bool, write_values: bool = True):
-        self.lib = _lib.load()
-        dev = y.device
-        self.n_dims = int(n_dims)
-        self.P = total_param_size(flow_types, n_dims, trainable_base)
-        self.B, self.H = int(h.shape[0]), int(h.shape[1])
-        assert dense_fusable(self.H, self.P, self.n_dims) and h.stride(1) == 1 and tuple(W.shape) == (self.H, self.P)
-        self.y, self.h, self.W, self.b = y, h, W.contiguous(), b
-        self.out = torch.empty((self.B,), dtype=torch.float32, device=dev) if write_values else None
-        self.sum2 = torch.zeros((2,), dtype=torch.float64, device=dev)  # {sum, non-finite}
-        self.sum = self.sum2[0:1]
-        self.partials = torch.zeros((max(2, int(self.lib.nfn_chain_workspace_doubles(self.B, self.n_dims, self.P))),),
-                                    dtype=torch.float64, device=dev)
-        self._ids, self._k = flow_ids(flow_types)
-        self._args = (
-            _ptr(y), _row_stride(y), _ptr(h), int(h.stride(0)), self.H, _ptr(self.W), _ptr(b), self.B, self.n_dims,
-            ctypes.cast(self._ids, ctypes.c_void_p), self._k, int(bool(trainable_base)), None, None, _ptr(self.out),
-            _ptr(self.sum2), _ptr(self.partials),
-        )
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.nfn_chain_logprob_dense_f32(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "nfn_chain_logprob_dense_f32")
-
-    def finish_sum(self, stream: Optional[int] = None) -> torch.Tensor:
-        """The launch's fp64 sum (finished inside the kernel: nothing to launch)."""
-        return self.sum
-
-    @property
-    def nonfinite(self) -> torch.Tensor:
-        """(1,) fp64: non-finite values among the last launch's log-densities."""
-        return self.sum2[1:2]
-
-
-class PosteriorDenseLauncher(DenseLauncher):
-    """Pre-bound fused DenseVariational->posterior launch (``nfn_posterior_lse_dense_f32``):
-    ``h`` (S, B, H), ``W`` (S, H, P), ``b`` (S, P) or None."""
-
-    def __init__(self, y: torch.Tensor, h: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor],
-                 flow_types: Sequence[str], n_dims: int, trainable_base: bool, write_values: bool = True):
-        self.lib = _lib.load()
-        dev = y.device
-        self.n_dims = int(n_dims)
-        self.P = total_param_size(flow_types, n_dims, trainable_base)
-        self.S, self.B, self.H = (int(v) for v in h.shape)
-        assert dense_fusable(self.H, self.P, self.n_dims) and h.is_contiguous()
-        assert tuple(W.shape) == (self.S, self.H, self.P) and (b is None or tuple(b.shape) == (self.S, self.P))
-        self.y, self.h, self.W = y, h, W.contiguous()
-        self.b = None if b is None else b.contiguous()
-        self.out = torch.empty((self.B,), dtype=torch.float32, device=dev) if write_values else None
-        self.sum2 = torch.zeros((2,), dtype=torch.float64, device=dev)  # {sum, non-finite}
-        self.sum = self.sum2[0:1]
-        self.partials = torch.zeros((max(2, int(self.lib.nfn_chain_workspace_doubles(self.B, self.n_dims, self.P))),),
-                                    dtype=torch.float64, device=dev)
-        self._ids, self._k = flow_ids(flow_types)
-        self._args = (
-            _ptr(y), _row_stride(y), _ptr(h), int(h.stride(0)), int(h.stride(1)), self.H, _ptr(self.W),
-            self.H * self.P, _ptr(self.b), self.P, self.S, self.B, self.n_dims, ctypes.cast(self._ids, ctypes.c_void_p),
-            self._k, int(bool(trainable_base)), None, None, _ptr(self.out), _ptr(self.sum2), _ptr(self.partials),
-        )
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.nfn_posterior_lse_dense_f32(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "nfn_posterior_lse_dense_f32")
-
-
 def chain_sample(eps, t, flow_types: Sequence[str], n_dims: int, trainable_base: bool, y_mean=None, y_std=None,
                  want_log_prob: bool = True):
     """Draw ``y ~ p(y | t)`` through the inverted flows for given standard-normal ``eps``
     (B or 1, d): returns ``(y (B, d), log_prob (B,) | None)`` (``nfn_chain_sample_f32``).
     A capability the reference lacks (its flows define no inverse)."""
     dev = _device()
-    P = total_param_size(flow_types, n_dims, trainable_base)
-    e = _prep_2d(eps, n_dims, "eps", dev)
-    t = _prep_2d(t, P, "t", dev) if P > 0 else torch.zeros((1, 1), dtype=torch.float32, device=dev)
-    B = max(int(e.shape[0]), int(t.shape[0]) if P > 0 else 1)
-    assert e.shape[0] in (1, B) and (P == 0 or t.shape[0] in (1, B)), "incompatible batch sizes"
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    e, t, t_stride, B, _ = _chain_inputs(eps, t, flow_types, n_dims, trainable_base, dev, name="eps")
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
     y = torch.empty((B, n_dims), dtype=torch.float32, device=dev)
     lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_log_prob else None
     ids, k = flow_ids(flow_types)
     rc = _lib.load().nfn_chain_sample_f32(
-        _ptr(e), _row_stride(e), _ptr(t), _row_stride(t) if P > 0 else 0, B, int(n_dims),
+        _ptr(e), _row_stride(e), _ptr(t), t_stride, B, int(n_dims),
         ctypes.cast(ids, ctypes.c_void_p), k, int(bool(trainable_base)), _ptr(ym), _ptr(ys), _ptr(y), _ptr(lp),
         _stream(),
     )
@@ -632,18 +591,13 @@ def chain_log_prob_grid(
     dev = _device()
     P = total_param_size(flow_types, n_dims, trainable_base)
     yg = _prep_2d(y_grid, n_dims, "y_grid", dev)
-    t = _prep_2d(t, P, "t", dev) if P > 0 else torch.zeros((1, 1), dtype=torch.float32, device=dev)
+    t, t_stride, B = _param_rows(t, P, dev)
     G = int(yg.shape[0])
-    B = int(t.shape[0]) if P > 0 else 1
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-        assert ym.numel() == n_dims and ys.numel() == n_dims
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
     out = torch.empty((G, B), dtype=torch.float32, device=dev)
     ids, k = flow_ids(flow_types)
     rc = _lib.load().nfn_chain_logprob_grid_f32(
-        _ptr(yg), int(yg.stride(0)) if G > 1 else 0, G, _ptr(t), _row_stride(t) if P > 0 else 0, B, int(n_dims),
+        _ptr(yg), int(yg.stride(0)) if G > 1 else 0, G, _ptr(t), t_stride, B, int(n_dims),
         ctypes.cast(ids, ctypes.c_void_p), k, int(bool(trainable_base)), _ptr(ym), _ptr(ys), _ptr(out), B,
         _stream(),
     )
@@ -651,17 +605,23 @@ def chain_log_prob_grid(
     return out
 
 
-def flow_forward_ldj(flow_type: str, z, t_k, n_dims: int, want_z: bool = True, want_ldj: bool = True):
-    """One bijector: ``(forward(z), forward_log_det_jacobian(z))`` (either may be None)."""
-    dev = _device()
+def _flow_inputs(flow_type: str, z, t_k, n_dims: int, device):
+    """``(z, t_k, B, param size)`` of a single-flow entry: ``z`` (B or 1, d), ``t_k`` (B or 1, p)."""
     ps = param_size(flow_type, n_dims)
-    z = _prep_2d(z, n_dims, "z", dev)
-    t_k = as_device_f32(t_k, dev)
+    z = _prep_2d(z, n_dims, "z", device)
+    t_k = as_device_f32(t_k, device)
     if t_k.dim() == 1:
         t_k = t_k.unsqueeze(0)
     assert t_k.shape[-1] == ps, f"{flow_type} flow needs {ps} params, got {t_k.shape[-1]}"
     B = max(z.shape[0], t_k.shape[0])
     assert z.shape[0] in (1, B) and t_k.shape[0] in (1, B), "incompatible batch sizes"
+    return z, t_k, B, ps
+
+
+def flow_forward_ldj(flow_type: str, z, t_k, n_dims: int, want_z: bool = True, want_ldj: bool = True):
+    """One bijector: ``(forward(z), forward_log_det_jacobian(z))`` (either may be None)."""
+    dev = _device()
+    z, t_k, B, ps = _flow_inputs(flow_type, z, t_k, n_dims, dev)
     z_out = torch.empty((B, n_dims), dtype=torch.float32, device=dev) if want_z else None
     ldj = torch.empty((B,), dtype=torch.float32, device=dev) if want_ldj else None
     lib = _lib.load()
@@ -679,14 +639,7 @@ def flow_vjp(flow_type: str, z: torch.Tensor, t_k: torch.Tensor, n_dims: int, g_
     per sample, (B, d) and (B, p), for ``L = sum_b <g_z[b], f(z_b)> + g_ldj[b] fldj(z_b)``
     (``g_z`` / ``g_ldj`` None => zero).  ``z`` / ``t_k`` as ``flow_forward_ldj`` takes them."""
     dev = _device()
-    ps = param_size(flow_type, n_dims)
-    z = _prep_2d(z, n_dims, "z", dev)
-    t_k = as_device_f32(t_k, dev)
-    if t_k.dim() == 1:
-        t_k = t_k.unsqueeze(0)
-    assert t_k.shape[-1] == ps, f"{flow_type} flow needs {ps} params, got {t_k.shape[-1]}"
-    B = max(z.shape[0], t_k.shape[0])
-    assert z.shape[0] in (1, B) and t_k.shape[0] in (1, B), "incompatible batch sizes"
+    z, t_k, B, ps = _flow_inputs(flow_type, z, t_k, n_dims, dev)
     gz = gl = None
     if g_z is not None:
         gz = as_device_f32(g_z, dev).expand(B, n_dims).contiguous()
@@ -726,21 +679,14 @@ class _FlowForwardLdj(torch.autograd.Function):
             return None, None, None, None
         dz, dt = flow_vjp(flow_type, z, t_k, n_dims, g_z, g_ldj, want_dz=need_z, want_dt=need_t)
         B = max(z.shape[0], t_k.shape[0])
-        if need_z and z.shape[0] == 1 and B > 1:
-            dz = dz.sum(0, keepdim=True)
-        if need_t and t_k.shape[0] == 1 and B > 1:
-            dt = dt.sum(0, keepdim=True)
-        return dz, dt, None, None
+        return _unbroadcast(dz, z, B), _unbroadcast(dt, t_k, B), None, None
 
 
 def flow_forward_ldj_diff(flow_type: str, z, t_k, n_dims: int):
     """Differentiable ``(forward(z), forward_log_det_jacobian(z))`` of one bijector: gradients
     w.r.t. ``z`` and ``t_k`` flow through ``torch.autograd`` via ``nfn_flow_vjp_f32``."""
     dev = _device()
-    z = _prep_2d(z, n_dims, "z", dev)
-    t_k = as_device_f32(t_k, dev)
-    if t_k.dim() == 1:
-        t_k = t_k.unsqueeze(0)
+    z, t_k, _, _ = _flow_inputs(flow_type, z, t_k, n_dims, dev)
     return _FlowForwardLdj.apply(z, t_k, flow_type, int(n_dims))
 
 
@@ -829,16 +775,11 @@ def posterior_lse(
     S, Bt = int(t_draws.shape[0]), int(t_draws.shape[1])
     B = max(y.shape[0], Bt)
     assert y.shape[0] in (1, B) and Bt in (1, B)
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-    want_sum = want_sum or want_nonfinite
-    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
-    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    ym, ys = _norm_stats(y_mean, y_std, n_dims, dev)
     lib = _lib.load()
-    # the workspace also enables the draw split (more parallelism for small B)
-    ws = _workspace(int(lib.nfn_posterior_workspace_doubles(B, n_dims, P)), dev)
+    # the workspace is always taken: it also enables the draw split (more parallelism for small B)
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite,
+                                 lambda: lib.nfn_posterior_workspace_doubles(B, n_dims, P), dev, workspace=True)
     ids, k = flow_ids(flow_types)
     rc = lib.nfn_posterior_lse_f32(
         _ptr(y), _row_stride(y), _ptr(t_draws), int(t_draws.stride(0)), 0 if Bt == 1 else int(t_draws.stride(1)),
@@ -858,7 +799,105 @@ def set_math_mode(mode: str) -> str:
     return "precise" if prev == 1 else "fast"
 
 
-class BijectorLauncher:
+# ---------------------------------------------------------------------------
+# Pre-bound launchers (the benchmark / serving loop)
+# ---------------------------------------------------------------------------
+
+class _Launcher:
+    """C-ABI calls bound once over fixed device buffers: all validation and pointer marshalling
+    happens in the constructor, ``launch()`` makes the bound calls in order on one stream (one
+    call for every launcher but ``FlowsLauncher``)."""
+
+    def __init__(self):
+        self.lib = _lib.load()
+        self._calls = []  # (bound C function, its arguments but the stream, its name)
+
+    def _bind(self, entry: str, *args) -> None:
+        self._calls.append((getattr(self.lib, entry), args, entry))
+
+    def launch(self, stream: Optional[int] = None) -> None:
+        st = stream if stream is not None else _stream()
+        for fn, args, entry in self._calls:
+            rc = fn(*args, st)
+            if rc != 0:
+                _lib.check(rc, entry)
+
+    @staticmethod
+    def _check_rows(y: torch.Tensor, n_dims: int, t: torch.Tensor, P: int) -> int:
+        """``y`` (B or 1, d) and ``t`` (B or 1, P) with unit column strides: returns B."""
+        assert y.dim() == 2 and y.shape[1] == n_dims and y.stride(1) == 1
+        assert t.dim() == 2 and t.shape[1] == P and t.stride(1) == 1
+        return max(int(y.shape[0]), int(t.shape[0]))
+
+
+class _SumLauncher(_Launcher):
+    """A launcher of an entry that ends in ``(out, out_sum, workspace, stream)``: ``launch()``
+    writes ``out`` (B,) and ``sum2`` = {fp64 sum, non-finite count}, finished in the kernel by
+    its last workgroup (``sum`` is ``sum2[0:1]``); ``partials`` is the launcher's own workspace."""
+
+    def _bind_sums(self, entry: str, *head, n_partials: int, write_values: bool, fused_sum: bool = True) -> None:
+        dev = self.y.device
+        self.out = torch.empty((self.B,), dtype=torch.float32, device=dev) if write_values else None
+        self.sum2 = torch.zeros((2,), dtype=torch.float64, device=dev)  # {sum, non-finite}
+        self.sum = self.sum2[0:1]
+        self.n_partials = int(n_partials)
+        self.partials = torch.zeros((max(2, self.n_partials),), dtype=torch.float64, device=dev)
+        self._sum_at = len(head) + 1  # where out_sum stands among the arguments (bind_sum)
+        self._bind(entry, *head, _ptr(self.out), _ptr(self.sum2) if fused_sum else None, _ptr(self.partials))
+
+    def finish_sum(self, stream: Optional[int] = None) -> torch.Tensor:
+        """The launch's fp64 sum (finished inside the kernel: nothing to launch)."""
+        return self.sum
+
+    @property
+    def nonfinite(self) -> torch.Tensor:
+        """(1,) fp64: non-finite values among the last launch's log-densities."""
+        return self.sum2[1:2]
+
+
+class DenseLauncher(_SumLauncher):
+    """Pre-bound fused Dense->chain launch over fixed device buffers (benchmark loop)."""
+
+    _entry = "nfn_chain_logprob_dense_f32"
+
+    def __init__(self, y: torch.Tensor, h: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor],
+                 flow_types: Sequence[str], n_dims: int, trainable_base: bool, write_values: bool = True):
+        super().__init__()
+        self.n_dims = int(n_dims)
+        self.P = total_param_size(flow_types, n_dims, trainable_base)
+        self.B, self.H = int(h.shape[-2]), int(h.shape[-1])
+        assert dense_fusable(self.H, self.P, self.n_dims)
+        self.y, self.h, self.W, self.b = y, h, W.contiguous(), b
+        layer = self._layer_args()
+        self._ids, k = flow_ids(flow_types)
+        self._bind_sums(self._entry, _ptr(y), _row_stride(y), *layer, self.B, self.n_dims,
+                        ctypes.cast(self._ids, ctypes.c_void_p), k, int(bool(trainable_base)), None, None,
+                        n_partials=self.lib.nfn_chain_workspace_doubles(self.B, self.n_dims, self.P),
+                        write_values=write_values)
+
+    def _layer_args(self) -> tuple:
+        """The entry's arguments for ``h``, ``W`` and ``b`` (checked here)."""
+        assert self.h.stride(1) == 1 and tuple(self.W.shape) == (self.H, self.P)
+        return _ptr(self.h), int(self.h.stride(0)), self.H, _ptr(self.W), _ptr(self.b)
+
+
+class PosteriorDenseLauncher(DenseLauncher):
+    """Pre-bound fused DenseVariational->posterior launch (``nfn_posterior_lse_dense_f32``):
+    ``h`` (S, B, H), ``W`` (S, H, P), ``b`` (S, P) or None."""
+
+    _entry = "nfn_posterior_lse_dense_f32"
+
+    def _layer_args(self) -> tuple:
+        h = self.h
+        self.S = int(h.shape[0])
+        assert h.dim() == 3 and h.is_contiguous() and tuple(self.W.shape) == (self.S, self.H, self.P)
+        assert self.b is None or tuple(self.b.shape) == (self.S, self.P)
+        self.b = None if self.b is None else self.b.contiguous()
+        return (_ptr(h), int(h.stride(0)), int(h.stride(1)), self.H, _ptr(self.W), self.H * self.P, _ptr(self.b),
+                self.P, self.S)
+
+
+class BijectorLauncher(_Launcher):
     """Pre-bound one-launch Chain bijector (``nfn_chain_fwd_ldj_f32``) over the layer's
     flow blocks of ``t`` — the Bijector API path (``Chain.forward`` +
     ``forward_log_det_jacobian``) for the benchmark: ``launch()`` writes ``z_out`` (B, d)
@@ -866,60 +905,40 @@ class BijectorLauncher:
 
     def __init__(self, z: torch.Tensor, t: torch.Tensor, flow_types: Sequence[str], n_dims: int,
                  trainable_base: bool):
-        self.lib = _lib.load()
-        dev = z.device
+        super().__init__()
         d = int(n_dims)
-        P = total_param_size(flow_types, d, trainable_base)
-        assert z.dim() == 2 and z.shape[1] == d and z.stride(1) == 1
-        assert t.dim() == 2 and t.shape[1] == P and t.stride(1) == 1
-        self.B = max(int(z.shape[0]), int(t.shape[0]))
-        # the layer's reversed layout: flow k's block offset within the row (_get_bijector)
-        off, offs = 2 * d if trainable_base else 0, [0] * len(flow_types)
-        for k in reversed(range(len(flow_types))):
-            offs[k] = off
-            off += param_size(flow_types[k], d)
+        self.B = self._check_rows(z, d, t, total_param_size(flow_types, d, trainable_base))
+        offs = flow_block_offsets(flow_types, d, trainable_base)
         self.z, self.t = z, t
-        self.z_out = torch.empty((self.B, d), dtype=torch.float32, device=dev)
-        self.ldj = torch.empty((self.B,), dtype=torch.float32, device=dev)
-        self._ids, self._k = flow_ids(flow_types)
+        self.z_out = torch.empty((self.B, d), dtype=torch.float32, device=z.device)
+        self.ldj = torch.empty((self.B,), dtype=torch.float32, device=z.device)
+        self._ids, k = flow_ids(flow_types)
         self._offs = (ctypes.c_int32 * max(1, len(offs)))(*offs)
-        self._args = (_ptr(z), _row_stride(z), _ptr(t), _row_stride(t), self.B, d,
-                      ctypes.cast(self._ids, ctypes.c_void_p), ctypes.cast(self._offs, ctypes.c_void_p), self._k,
-                      _ptr(self.z_out), _ptr(self.ldj))
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.nfn_chain_fwd_ldj_f32(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "nfn_chain_fwd_ldj_f32")
+        self._bind("nfn_chain_fwd_ldj_f32", _ptr(z), _row_stride(z), _ptr(t), _row_stride(t), self.B, d,
+                   ctypes.cast(self._ids, ctypes.c_void_p), ctypes.cast(self._offs, ctypes.c_void_p), k,
+                   _ptr(self.z_out), _ptr(self.ldj))
 
 
-class GridLauncher:
+class GridLauncher(_Launcher):
     """Pre-bound density grid (``nfn_chain_logprob_grid_f32``) for the benchmark: the
     ``log_prob`` of each of G grid values under each of B parameter rows, (G, B) out — the
     evaluation ``flow_plotting.plot_model`` makes (``evaluation/visualization/flow_plotting.py:33-53``)."""
 
     def __init__(self, y_grid: torch.Tensor, t: torch.Tensor, flow_types: Sequence[str], n_dims: int,
                  trainable_base: bool):
-        self.lib = _lib.load()
+        super().__init__()
         d = int(n_dims)
-        P = total_param_size(flow_types, d, trainable_base)
-        assert y_grid.dim() == 2 and y_grid.shape[1] == d and y_grid.stride(1) == 1
-        assert t.dim() == 2 and t.shape[1] == P and t.stride(1) == 1
+        self._check_rows(y_grid, d, t, total_param_size(flow_types, d, trainable_base))
         self.G, self.B = int(y_grid.shape[0]), int(t.shape[0])
         self.y_grid, self.t = y_grid, t
         self.out = torch.empty((self.G, self.B), dtype=torch.float32, device=t.device)
-        self._ids, self._k = flow_ids(flow_types)
-        self._args = (_ptr(y_grid), int(y_grid.stride(0)) if self.G > 1 else 0, self.G, _ptr(t), _row_stride(t),
-                      self.B, d, ctypes.cast(self._ids, ctypes.c_void_p), self._k, int(bool(trainable_base)),
-                      None, None, _ptr(self.out), self.B)
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.nfn_chain_logprob_grid_f32(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "nfn_chain_logprob_grid_f32")
+        self._ids, k = flow_ids(flow_types)
+        self._bind("nfn_chain_logprob_grid_f32", _ptr(y_grid), int(y_grid.stride(0)) if self.G > 1 else 0, self.G,
+                   _ptr(t), _row_stride(t), self.B, d, ctypes.cast(self._ids, ctypes.c_void_p), k,
+                   int(bool(trainable_base)), None, None, _ptr(self.out), self.B)
 
 
-class FlowsLauncher:
+class FlowsLauncher(_Launcher):
     """Pre-bound flow-by-flow Bijector path for the benchmark: the Chain's K flows as K
     single-flow launches (``nfn_flow_fwd_ldj_f32``, PlanarFlow.py:68-80 / RadialFlow.py:50-70 /
     AffineFlow.py called one bijector at a time), flow k reading its own parameters and the
@@ -938,38 +957,31 @@ class FlowsLauncher:
 
     def __init__(self, z: torch.Tensor, t: torch.Tensor, flow_types: Sequence[str], n_dims: int,
                  trainable_base: bool, separate: bool = False, params: Optional[str] = None):
-        self.lib = _lib.load()
+        super().__init__()
         dev = z.device
         d = int(n_dims)
         self.mode = params or ("separate" if separate else "views")
         assert self.mode in ("views", "separate", "strided")
         P = total_param_size(flow_types, d, trainable_base)
-        assert z.dim() == 2 and z.shape[1] == d and z.stride(1) == 1
-        assert t.dim() == 2 and t.shape[1] == P and t.stride(1) == 1
-        B = max(int(z.shape[0]), int(t.shape[0]))
-        self.B, K = B, len(flow_types)
-        base = 2 * d if trainable_base else 0
-        off, offs = base, [0] * K
-        for k in reversed(range(K)):
-            offs[k] = off
-            off += param_size(flow_types[k], d)
+        self.B = B = self._check_rows(z, d, t, P)
+        K = len(flow_types)
+        widths = [param_size(f, d) for f in flow_types]
+        offs = flow_block_offsets(flow_types, d, trainable_base)
         zs = [torch.empty((B, d), dtype=torch.float32, device=dev) for _ in range(2)]
         self.ldj = torch.empty((max(1, K), B), dtype=torch.float32, device=dev)
         self.z_out = zs[(K - 1) % 2] if K else z
-        self._calls = []
-        self._split = None
         self.params = []  # the flows' contiguous parameter tensors (kept alive here)
-        if self.mode == "views" and not split_pays([param_size(f, d) for f in flow_types], _row_stride(t) or P):
+        if self.mode == "views" and not split_pays(widths, _row_stride(t) or P):
             self.mode = "strided"  # the package's flows read such blocks straight from the rows
         if self.mode != "strided" and K:
             # blocks in row order: flow K-1 first (the layer's reversed layout)
             order = sorted(range(K), key=lambda k: offs[k])
-            widths = [param_size(flow_types[k], d) for k in order]
-            tb = t[:, base:]
-            blocks = split_blocks(tb, widths)
+            row_widths = [widths[k] for k in order]
+            tb = t[:, P - sum(widths):]  # the flows' columns follow the base's
+            blocks = split_blocks(tb, row_widths)
             if self.mode == "views":
-                self._split = (_ptr(tb), _row_stride(tb), B, (ctypes.c_int32 * len(widths))(*widths), len(widths),
-                               _ptr(blocks[0]))
+                self._bind("nfn_split_blocks_f32", _ptr(tb), _row_stride(tb), B,
+                           (ctypes.c_int32 * K)(*row_widths), K, _ptr(blocks[0]))
             by_flow = {k: blocks[i] for i, k in enumerate(order)}
             self.params = [by_flow[k] for k in range(K)]
         zin = z
@@ -978,25 +990,14 @@ class FlowsLauncher:
             if self.mode == "strided":
                 pptr, pstride = _ptr(t) + 4 * offs[k], _row_stride(t)
             else:
-                pptr, pstride = _ptr(self.params[k]), param_size(f, d)
-            self._calls.append((FLOW_IDS[f], _ptr(zin), _row_stride(zin), pptr, pstride, B, d, _ptr(zo),
-                                _ptr(self.ldj[k])))
+                pptr, pstride = _ptr(self.params[k]), widths[k]
+            self._bind("nfn_flow_fwd_ldj_f32", FLOW_IDS[f], _ptr(zin), _row_stride(zin), pptr, pstride, B, d,
+                       _ptr(zo), _ptr(self.ldj[k]))
             zin = zo
-        self.bytes_per_launch = float(B) * sum(4 * d + 4 * param_size(f, d) + 4 * d + 4 for f in flow_types)
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        st = stream if stream is not None else _stream()
-        if self._split is not None:
-            rc = self.lib.nfn_split_blocks_f32(*self._split, st)
-            if rc != 0:
-                _lib.check(rc, "nfn_split_blocks_f32")
-        for args in self._calls:
-            rc = self.lib.nfn_flow_fwd_ldj_f32(*args, st)
-            if rc != 0:
-                _lib.check(rc, "nfn_flow_fwd_ldj_f32")
+        self.bytes_per_launch = float(B) * sum(4 * d + 4 * w + 4 * d + 4 for w in widths)
 
 
-class ChainLauncher:
+class ChainLauncher(_SumLauncher):
     """Pre-bound fused-chain launch for repeated evaluation of fixed device
     buffers (the benchmark / serving loop): all validation and pointer
     marshalling happens once; ``launch()`` is a single C-ABI call.
@@ -1007,49 +1008,29 @@ class ChainLauncher:
     def __init__(self, y: torch.Tensor, t: torch.Tensor, flow_types: Sequence[str], n_dims: int,
                  trainable_base: bool, write_values: bool = True, draws: Optional[int] = None,
                  fused_sum: bool = True):
-        self.lib = _lib.load()
-        dev = y.device
+        super().__init__()
         self.n_dims = int(n_dims)
         self.P = total_param_size(flow_types, n_dims, trainable_base)
         self.posterior = draws is not None
-        assert y.dim() == 2 and y.shape[1] == n_dims and y.stride(1) == 1
         if self.posterior:
+            assert y.dim() == 2 and y.shape[1] == n_dims and y.stride(1) == 1
             assert t.dim() == 3 and t.shape[0] == draws and t.shape[2] == self.P and t.stride(2) == 1
             self.B = max(int(y.shape[0]), int(t.shape[1]))
+            entry, sizes = "nfn_posterior_lse_f32", self.lib.nfn_posterior_workspace_doubles
+            rows = (_ptr(t), int(t.stride(0)), 0 if t.shape[1] == 1 else int(t.stride(1)), int(draws))
         else:
-            assert t.dim() == 2 and t.shape[1] == self.P and t.stride(1) == 1
-            self.B = max(int(y.shape[0]), int(t.shape[0]))
+            self.B = self._check_rows(y, n_dims, t, self.P)
+            entry, sizes = "nfn_chain_logprob_f32", self.lib.nfn_chain_workspace_doubles
+            rows = (_ptr(t), _row_stride(t))
         self.y, self.t = y, t
-        self.out = torch.empty((self.B,), dtype=torch.float32, device=dev) if write_values else None
-        self.sum2 = torch.zeros((2,), dtype=torch.float64, device=dev)  # {sum, non-finite}
-        self.sum = self.sum2[0:1]
-        fn_ws = self.lib.nfn_posterior_workspace_doubles if self.posterior else self.lib.nfn_chain_workspace_doubles
-        self.n_partials = int(fn_ws(self.B, self.n_dims, self.P))
-        self.partials = torch.zeros((max(2, self.n_partials),), dtype=torch.float64, device=dev)
         self.fused_sum = fused_sum
-        self._ids, self._k = flow_ids(flow_types)
-        self._ids_p = ctypes.cast(self._ids, ctypes.c_void_p)
-        self._trainable = int(bool(trainable_base))
-        if self.posterior:
-            self._args = (
-                _ptr(y), _row_stride(y), _ptr(t), int(t.stride(0)), 0 if t.shape[1] == 1 else int(t.stride(1)),
-                int(draws), self.B, self.n_dims, self._ids_p, self._k, self._trainable, None, None,
-                _ptr(self.out), _ptr(self.sum2) if fused_sum else None, _ptr(self.partials),
-            )
-            self._fn = self.lib.nfn_posterior_lse_f32
-        else:
-            self._args = (
-                _ptr(y), _row_stride(y), _ptr(t), _row_stride(t), self.B, self.n_dims, self._ids_p, self._k,
-                self._trainable, None, None, _ptr(self.out), _ptr(self.sum2) if fused_sum else None,
-                _ptr(self.partials),
-            )
-            self._fn = self.lib.nfn_chain_logprob_f32
-        self._sum_args = (_ptr(self.partials), _ptr(self.sum2))
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self._fn(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "fused chain launch")
+        self._ids, k = flow_ids(flow_types)
+        self._bind_sums(entry, _ptr(y), _row_stride(y), *rows, self.B, self.n_dims,
+                        ctypes.cast(self._ids, ctypes.c_void_p), k, int(bool(trainable_base)), None, None,
+                        n_partials=sizes(self.B, self.n_dims, self.P), write_values=write_values,
+                        fused_sum=fused_sum)
+        self._reduce = _Launcher()
+        self._reduce._bind("nfn_reduce_partials_f64", _ptr(self.partials), _ptr(self.sum2))
 
     def bind_sum(self, target: torch.Tensor) -> None:
         """Make later launches finish their ``{sum, non-finite count}`` into ``target[0:2]``
@@ -1057,8 +1038,8 @@ class ChainLauncher:
         no copy kernels between the chain kernel and the collective."""
         assert self.fused_sum, "bind_sum needs the in-kernel finish"
         assert target.dtype == torch.float64 and target.is_contiguous() and target.numel() >= 2
-        i = 14 if self.posterior else 12
-        self._args = self._args[:i] + (_ptr(target),) + self._args[i + 1:]
+        fn, args, entry = self._calls[0]
+        self._calls[0] = (fn, args[:self._sum_at] + (_ptr(target),) + args[self._sum_at + 1:], entry)
         self.sum2, self.sum = target[0:2], target[0:1]
 
     def finish_sum(self, stream: Optional[int] = None) -> torch.Tensor:
@@ -1066,50 +1047,34 @@ class ChainLauncher:
         ``fused_sum=False`` the launch writes only the partials and this reduces them
         (``nfn_reduce_partials_f64``, the same summation order and bits)."""
         if not self.fused_sum:
-            rc = self.lib.nfn_reduce_partials_f64(*self._sum_args, stream if stream is not None else _stream())
-            if rc != 0:
-                _lib.check(rc, "nfn_reduce_partials_f64")
+            self._reduce.launch(stream)
         return self.sum
 
-    @property
-    def nonfinite(self) -> torch.Tensor:
-        """(1,) fp64: non-finite values among the last launch's log-densities."""
-        return self.sum2[1:2]
 
-
-class GradLauncher:
+class GradLauncher(_Launcher):
     """Pre-bound fused-backward launch over fixed device buffers (the training-step
     benchmark): ``launch()`` writes ``grad_t`` (B, P) and ``grad_y`` (B, d) for the
     upstream gradient ``g_out`` (B,) — one C-ABI call."""
 
     def __init__(self, y: torch.Tensor, t: torch.Tensor, flow_types: Sequence[str], n_dims: int,
                  trainable_base: bool, g_out: Optional[torch.Tensor] = None, write_logp: bool = False):
-        self.lib = _lib.load()
+        super().__init__()
         dev = y.device
         self.n_dims = int(n_dims)
         self.P = total_param_size(flow_types, n_dims, trainable_base)
-        assert y.dim() == 2 and y.shape[1] == n_dims and y.stride(1) == 1
-        assert t.dim() == 2 and t.shape[1] == self.P and t.stride(1) == 1
-        self.B = max(int(y.shape[0]), int(t.shape[0]))
+        self.B = self._check_rows(y, n_dims, t, self.P)
         assert g_out is None or (g_out.numel() == self.B and g_out.is_contiguous())
         self.y, self.t, self.g_out = y, t, g_out
         self.logp = torch.empty((self.B,), dtype=torch.float32, device=dev) if write_logp else None
         self.grad_t = torch.empty((self.B, self.P), dtype=torch.float32, device=dev)
         self.grad_y = torch.empty((self.B, self.n_dims), dtype=torch.float32, device=dev)
-        self._ids, self._k = flow_ids(flow_types)
-        self._args = (
-            _ptr(y), _row_stride(y), _ptr(t), _row_stride(t), self.B, self.n_dims,
-            ctypes.cast(self._ids, ctypes.c_void_p), self._k, int(bool(trainable_base)), None, None,
-            _ptr(g_out), _ptr(self.logp), _ptr(self.grad_t), self.P, _ptr(self.grad_y),
-        )
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.nfn_chain_logprob_grad_f32(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "nfn_chain_logprob_grad_f32")
+        self._ids, k = flow_ids(flow_types)
+        self._bind("nfn_chain_logprob_grad_f32", _ptr(y), _row_stride(y), _ptr(t), _row_stride(t), self.B,
+                   self.n_dims, ctypes.cast(self._ids, ctypes.c_void_p), k, int(bool(trainable_base)), None, None,
+                   _ptr(g_out), _ptr(self.logp), _ptr(self.grad_t), self.P, _ptr(self.grad_y))
 
 
-class DenseGradLauncher:
+class DenseGradLauncher(_Launcher):
     """Pre-bound fused backward through the output Dense layer
     (``nfn_chain_logprob_dense_grad_f32``) over fixed device buffers (the training-step
     benchmark): ``launch()`` writes ``grad_h`` (B, H), ``grad_W`` (H, P), ``grad_b`` (P,)
@@ -1118,7 +1083,7 @@ class DenseGradLauncher:
 
     def __init__(self, y: torch.Tensor, h: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor],
                  flow_types: Sequence[str], n_dims: int, trainable_base: bool, g_out: Optional[torch.Tensor] = None):
-        self.lib = _lib.load()
+        super().__init__()
         dev = y.device
         self.n_dims = int(n_dims)
         self.P = total_param_size(flow_types, n_dims, trainable_base)
@@ -1133,50 +1098,26 @@ class DenseGradLauncher:
         self.grad_y = torch.empty((self.B, self.n_dims), dtype=torch.float32, device=dev)
         self.ws = torch.empty((max(1, int(self.lib.nfn_dense_grad_workspace_floats(self.B, self.H, self.P))),),
                               dtype=torch.float32, device=dev)
-        self._ids, self._k = flow_ids(flow_types)
-        self._args = (
-            _ptr(y), _row_stride(y), _ptr(h), int(h.stride(0)), self.H, _ptr(self.W), _ptr(b), self.B, self.n_dims,
-            ctypes.cast(self._ids, ctypes.c_void_p), self._k, int(bool(trainable_base)), None, None, _ptr(g_out),
-            None, _ptr(self.grad_h), self.H, _ptr(self.grad_W), _ptr(self.grad_b), _ptr(self.grad_y), _ptr(self.ws),
-        )
-
-    def launch(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.nfn_chain_logprob_dense_grad_f32(*self._args, stream if stream is not None else _stream())
-        if rc != 0:
-            _lib.check(rc, "nfn_chain_logprob_dense_grad_f32")
+        self._ids, k = flow_ids(flow_types)
+        self._bind("nfn_chain_logprob_dense_grad_f32", _ptr(y), _row_stride(y), _ptr(h), int(h.stride(0)), self.H,
+                   _ptr(self.W), _ptr(b), self.B, self.n_dims, ctypes.cast(self._ids, ctypes.c_void_p), k,
+                   int(bool(trainable_base)), None, None, _ptr(g_out), None, _ptr(self.grad_h), self.H,
+                   _ptr(self.grad_W), _ptr(self.grad_b), _ptr(self.grad_y), _ptr(self.ws))
 
 
 # ---------------------------------------------------------------------------
 # Kernel mixture network: Gaussian-kernel mixture log_prob (nfn_mixture.hip)
 # ---------------------------------------------------------------------------
 
-def _mixture_inputs(y, logits, locs, scales, y_mean, y_std, dev):
-    """Device tensors in the C ABI's conventions: ``locs`` (M, d), ``scales`` (M,), ``logits``
-    (B, M) with a unit column stride (a column view of a wider tensor stays a view), ``y``
-    (B or 1, d).  One logit row against a batch of ``y`` is expanded (the ABI's logits rows
-    have a stride >= M)."""
-    locs = as_device_f32(locs, dev)
+def _kernel_params(locs, scales, device):
+    """``(locs (M, d), scales (M,), M, d)`` in the C ABI's conventions (both contiguous)."""
+    locs = as_device_f32(locs, device)
     assert locs.dim() == 2, "locs must be (M, n_dims)"
     locs = locs.contiguous()
     M, d = int(locs.shape[0]), int(locs.shape[1])
-    scales = as_device_f32(scales, dev).reshape(-1).contiguous()
+    scales = as_device_f32(scales, device).reshape(-1).contiguous()
     assert scales.numel() == M, f"scales must have {M} elements"
-    y = _prep_2d(y, d, "y", dev)
-    logits = _prep_2d(logits, M, "logits", dev)
-    B = max(int(y.shape[0]), int(logits.shape[0]))
-    assert y.shape[0] in (1, B) and logits.shape[0] in (1, B), "incompatible batch sizes"
-    if logits.shape[0] != B:
-        logits = logits.expand(B, M).contiguous()
-    rs = int(logits.stride(0)) if B > 1 else M
-    if rs < M:  # an expanded (stride-0) batch
-        logits = logits.contiguous()
-        rs = M
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-        assert ym.numel() == d and ys.numel() == d
-    return y, logits, rs, locs, scales, ym, ys, B, d, M
+    return locs, scales, M, d
 
 
 def kernel_mixture_log_prob(y, logits, locs, scales, y_mean=None, y_std=None, want_values: bool = True,
@@ -1188,12 +1129,11 @@ def kernel_mixture_log_prob(y, logits, locs, scales, y_mean=None, y_std=None, wa
     include/nfn.h).  Returns as :func:`chain_log_prob`: ``(log_prob | None, sum | None)``,
     plus the non-finite count with ``want_nonfinite``."""
     dev = _device()
-    y, logits, rs, locs, scales, ym, ys, B, d, M = _mixture_inputs(y, logits, locs, scales, y_mean, y_std, dev)
-    want_sum = want_sum or want_nonfinite or not want_values
-    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
-    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    locs, scales, M, d = _kernel_params(locs, scales, dev)
+    y, logits, rs, ym, ys, B = _row_inputs(y, logits, M, d, y_mean, y_std, dev, "logits")
     lib = _lib.load()
-    ws = _workspace(int(lib.nfn_kernel_mixture_workspace_doubles(B, d, M)), dev) if want_sum else None
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite or not want_values,
+                                 lambda: lib.nfn_kernel_mixture_workspace_doubles(B, d, M), dev)
     rc = lib.nfn_kernel_mixture_logprob_f32(
         _ptr(y), _row_stride(y), _ptr(logits), rs, _ptr(locs), _ptr(scales), B, d, M, _ptr(ym), _ptr(ys),
         _ptr(out), _ptr(osum), _ptr(ws), _stream(),
@@ -1210,11 +1150,9 @@ def kernel_mixture_log_prob_grad(y, logits, locs, scales, y_mean=None, y_std=Non
     (M,))``.  ``dL/dscales`` is a batch sum: per-workgroup partials and a fixed-order final
     sum, so the same inputs give the same bits."""
     dev = _device()
-    y, logits, rs, locs, scales, ym, ys, B, d, M = _mixture_inputs(y, logits, locs, scales, y_mean, y_std, dev)
-    g = None
-    if g_out is not None:
-        g = as_device_f32(g_out, dev).reshape(-1).contiguous()
-        assert g.numel() == B, f"g_out must have {B} elements"
+    locs, scales, M, d = _kernel_params(locs, scales, dev)
+    y, logits, rs, ym, ys, B = _row_inputs(y, logits, M, d, y_mean, y_std, dev, "logits")
+    g = _upstream(g_out, B, dev)
     lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_logp else None
     gl = torch.empty((B, M), dtype=torch.float32, device=dev) if want_grad_logits else None
     gy = torch.empty((B, d), dtype=torch.float32, device=dev) if want_grad_y else None
@@ -1252,55 +1190,23 @@ class _KernelMixtureLogProb(torch.autograd.Function):
                                                      want_grad_logits=need_l, want_grad_y=need_y,
                                                      want_grad_scales=need_s)
         B = g.shape[0]
-        if need_y and y.shape[0] == 1 and B > 1:
-            gy = gy.sum(0, keepdim=True)
-        if need_l and logits.shape[0] == 1 and B > 1:
-            gl = gl.sum(0, keepdim=True)
-        return (gy if need_y else None), (gl if need_l else None), None, (gs if need_s else None), None, None
+        return _unbroadcast(gy, y, B), _unbroadcast(gl, logits, B), None, gs, None, None
 
 
 def kernel_mixture_log_prob_diff(y, logits, locs, scales, y_mean=None, y_std=None):
     """Differentiable fused mixture ``log_prob`` (B,): gradients w.r.t. ``logits``, ``scales``
     and ``y`` come from the fused backward kernel."""
     dev = _device()
-    locs = as_device_f32(locs, dev).contiguous()
-    M, d = int(locs.shape[0]), int(locs.shape[1])
+    locs, scales, M, d = _kernel_params(locs, scales, dev)
     y = _prep_2d(y, d, "y", dev)
     logits = _prep_2d(logits, M, "logits", dev)
-    scales = as_device_f32(scales, dev).reshape(-1)
-    if y_mean is not None:
-        y_mean = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        y_std = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    y_mean, y_std = _norm_stats(y_mean, y_std, d, dev)
     return _KernelMixtureLogProb.apply(y, logits, locs, scales, y_mean, y_std)
 
 
 # ---------------------------------------------------------------------------
 # Mixture density network: Gaussian-mixture log_prob (nfn_gmm.hip)
 # ---------------------------------------------------------------------------
-
-def _gmm_inputs(y, t, n_centers, n_dims, y_mean, y_std, dev):
-    """Device tensors in the C ABI's conventions: ``t`` (B, P = K (2 d + 1)) with a unit
-    column stride (a column view of a wider tensor stays a view), ``y`` (B or 1, d).  One
-    parameter row against a batch of ``y`` is expanded (the ABI's rows have a stride >= P)."""
-    K, d = int(n_centers), int(n_dims)
-    P = K * (2 * d + 1)
-    y = _prep_2d(y, d, "y", dev)
-    t = _prep_2d(t, P, "t", dev)
-    B = max(int(y.shape[0]), int(t.shape[0]))
-    assert y.shape[0] in (1, B) and t.shape[0] in (1, B), "incompatible batch sizes"
-    if t.shape[0] != B:
-        t = t.expand(B, P).contiguous()
-    rs = int(t.stride(0)) if B > 1 else P
-    if rs < P:  # an expanded (stride-0) batch
-        t = t.contiguous()
-        rs = P
-    ym = ys = None
-    if y_mean is not None:
-        ym = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        ys = as_device_f32(y_std, dev).reshape(-1).contiguous()
-        assert ym.numel() == d and ys.numel() == d
-    return y, t, rs, ym, ys, B, d, K, P
-
 
 def gaussian_mixture_log_prob(y, t, n_centers, n_dims, y_mean=None, y_std=None, want_values: bool = True,
                               want_nonfinite: bool = False, want_sum: bool = False):
@@ -1310,12 +1216,11 @@ def gaussian_mixture_log_prob(y, t, n_centers, n_dims, y_mean=None, y_std=None, 
     :func:`chain_log_prob`: ``(log_prob | None, sum | None)``, plus the non-finite count with
     ``want_nonfinite``."""
     dev = _device()
-    y, t, rs, ym, ys, B, d, K, _ = _gmm_inputs(y, t, n_centers, n_dims, y_mean, y_std, dev)
-    want_sum = want_sum or want_nonfinite or not want_values
-    out = torch.empty((B,), dtype=torch.float32, device=dev) if want_values else None
-    osum = torch.empty((2,), dtype=torch.float64, device=dev) if want_sum else None
+    K, d = int(n_centers), int(n_dims)
+    y, t, rs, ym, ys, B = _row_inputs(y, t, K * (2 * d + 1), d, y_mean, y_std, dev, "t")
     lib = _lib.load()
-    ws = _workspace(int(lib.nfn_gaussian_mixture_workspace_doubles(B, d, K)), dev) if want_sum else None
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite or not want_values,
+                                 lambda: lib.nfn_gaussian_mixture_workspace_doubles(B, d, K), dev)
     rc = lib.nfn_gaussian_mixture_logprob_f32(
         _ptr(y), _row_stride(y), _ptr(t), rs, B, d, K, _ptr(ym), _ptr(ys), _ptr(out), _ptr(osum), _ptr(ws),
         _stream(),
@@ -1329,11 +1234,10 @@ def gaussian_mixture_log_prob_grad(y, t, n_centers, n_dims, y_mean=None, y_std=N
     """Fused backward of :func:`gaussian_mixture_log_prob` for ``L = sum_b g_out[b] *
     log_prob_b`` (``g_out`` None => ones): ``(log_prob | None, dL/dt (B, P), dL/dy (B, d))``."""
     dev = _device()
-    y, t, rs, ym, ys, B, d, K, P = _gmm_inputs(y, t, n_centers, n_dims, y_mean, y_std, dev)
-    g = None
-    if g_out is not None:
-        g = as_device_f32(g_out, dev).reshape(-1).contiguous()
-        assert g.numel() == B, f"g_out must have {B} elements"
+    K, d = int(n_centers), int(n_dims)
+    P = K * (2 * d + 1)
+    y, t, rs, ym, ys, B = _row_inputs(y, t, P, d, y_mean, y_std, dev, "t")
+    g = _upstream(g_out, B, dev)
     lp = torch.empty((B,), dtype=torch.float32, device=dev) if want_logp else None
     gt = torch.empty((B, P), dtype=torch.float32, device=dev) if want_grad_t else None
     gy = torch.empty((B, d), dtype=torch.float32, device=dev) if want_grad_y else None
@@ -1364,11 +1268,7 @@ class _GaussianMixtureLogProb(torch.autograd.Function):
         _, gt, gy = gaussian_mixture_log_prob_grad(y, t, n_centers, n_dims, y_mean, y_std, g_out=g.contiguous(),
                                                    want_grad_t=need_t, want_grad_y=need_y)
         B = g.shape[0]
-        if need_y and y.shape[0] == 1 and B > 1:
-            gy = gy.sum(0, keepdim=True)
-        if need_t and t.shape[0] == 1 and B > 1:
-            gt = gt.sum(0, keepdim=True)
-        return (gy if need_y else None), (gt if need_t else None), None, None, None, None
+        return _unbroadcast(gy, y, B), _unbroadcast(gt, t, B), None, None, None, None
 
 
 def gaussian_mixture_log_prob_diff(y, t, n_centers, n_dims, y_mean=None, y_std=None):
@@ -1378,7 +1278,5 @@ def gaussian_mixture_log_prob_diff(y, t, n_centers, n_dims, y_mean=None, y_std=N
     K, d = int(n_centers), int(n_dims)
     y = _prep_2d(y, d, "y", dev)
     t = _prep_2d(t, K * (2 * d + 1), "t", dev)
-    if y_mean is not None:
-        y_mean = as_device_f32(y_mean, dev).reshape(-1).contiguous()
-        y_std = as_device_f32(y_std, dev).reshape(-1).contiguous()
+    y_mean, y_std = _norm_stats(y_mean, y_std, d, dev)
     return _GaussianMixtureLogProb.apply(y, t, K, d, y_mean, y_std)
