@@ -64,6 +64,16 @@
  *   nfn_posterior_lse_f32  <- BayesianNNEstimator.score per-sample logsumexp
  *                                                    estimators/BayesianNNEstimator.py:65-76,
  *                                                    evaluation/scorers.py:13-27
+ *   nfn_posterior_lse_gaussian_mixture_f32
+ *                          <- that score with a GaussianMixtureLayer as the density layer
+ *                             (BayesMixtureDensityNetwork)
+ *                                                    estimators/BayesMixtureDensityNetwork.py,
+ *                                                    estimators/BayesianNNEstimator.py:65-76
+ *   nfn_posterior_lse_kernel_mixture_f32
+ *                          <- that score with a GaussianKernelsLayer as the density layer
+ *                             (BayesKernelMixtureNetwork)
+ *                                                    estimators/BayesKernelMixtureNetwork.py,
+ *                                                    estimators/BayesianNNEstimator.py:65-76
  *   nfn_comm_* /
  *   nfn_allreduce_mean     <- the mean of score()/mle_log_likelihood_score over a batch
  *                             sharded across GPUs (one RCCL all-reduce of {sum, count})
@@ -103,7 +113,9 @@ extern "C" {
 /* Library version as MAJOR*10000 + MINOR*100 + PATCH.
  *   203 (0.2.3): + nfn_set_launch_events (additive, measurement hook); later also, with
  *                no version change (additive, every earlier entry unchanged), the four
- *                nfn_kernel_mixture_* entries and the three nfn_gaussian_mixture_* entries.
+ *                nfn_kernel_mixture_* entries, the three nfn_gaussian_mixture_* entries,
+ *                and nfn_posterior_lse_gaussian_mixture_f32 / nfn_posterior_lse_kernel_mixture_f32
+ *                with their two workspace queries.
  *   202 (0.2.2): + nfn_flow_vjp_f32 (additive).
  *   201 (0.2.1): + nfn_split_blocks_f32 (additive; every 200 entry point unchanged).
  *   200 (0.2.0): out_sum is a device double[2] {sum, non-finite count} (was double[1]);
@@ -431,6 +443,40 @@ int32_t nfn_gaussian_mixture_logprob_grad_f32(const float* y, int64_t y_bstride,
                                               int64_t B, int32_t d, int32_t K, const float* y_mean,
                                               const float* y_std, const float* g_out, float* out_logp, float* grad_t,
                                               int64_t grad_t_rowstride, float* grad_y, void* stream);
+
+/*
+ * Posterior score of the two mixture layers (BayesianNNEstimator.score,
+ * estimators/BayesianNNEstimator.py:65-76), one fused kernel each:
+ *   out_lse[b] = logsumexp_s(logp(y_b | row(s, b))) - log S,   s = 0 .. S-1
+ * where logp is exactly what nfn_gaussian_mixture_logprob_f32 / nfn_kernel_mixture_logprob_f32
+ * compute for that row (the kept bandwidth quirk, -inf logits removing components, and
+ * - sum_j log y_std_j when y_mean / y_std are given; both or neither), with ONE exception: a row
+ * whose logits are ALL -inf has no component left, and its logp is taken as -inf (density 0),
+ * where the single-draw entries return NaN (-inf - -inf).
+ *   t / logits : draw s, sample b at base + s * drawstride + b * rowstride floats, rowstride >= the
+ *                row width (P = K * (2*d + 1), respectively M), drawstride >= 0; the rows do not
+ *                broadcast over the batch
+ *   y          : (B or 1, d) rows at y_bstride floats (0 = broadcast), read once per sample
+ *   out_lse (nullable), out_sum (nullable), workspace : as for nfn_chain_logprob_f32, with
+ *                workspace a device double[nfn_posterior_*_workspace_doubles(B, d, K or M)];
+ *                out_sum is bitwise deterministic and the same with and without out_lse
+ * Non-finite draws follow tf.reduce_logsumexp: a draw whose logp is -inf (an all -inf logit
+ * row among them) drops out of the sum, S staying the divisor;
+ * all S draws -inf give -inf; any NaN draw gives NaN; a +inf draw gives +inf.  out_sum[1]
+ * counts the non-finite results.
+ * Limits: those of the single-draw entries, and S >= 1 (else NFN_E_SHAPE).
+ */
+int64_t nfn_posterior_gaussian_mixture_workspace_doubles(int64_t B, int32_t d, int32_t K);
+int32_t nfn_posterior_lse_gaussian_mixture_f32(const float* y, int64_t y_bstride, const float* t,
+                                               int64_t t_drawstride, int64_t t_rowstride, int32_t S, int64_t B,
+                                               int32_t d, int32_t K, const float* y_mean, const float* y_std,
+                                               float* out_lse, double* out_sum, double* workspace, void* stream);
+int64_t nfn_posterior_kernel_mixture_workspace_doubles(int64_t B, int32_t d, int32_t M);
+int32_t nfn_posterior_lse_kernel_mixture_f32(const float* y, int64_t y_bstride, const float* logits,
+                                             int64_t logits_drawstride, int64_t logits_rowstride, int32_t S,
+                                             const float* locs, const float* scales, int64_t B, int32_t d, int32_t M,
+                                             const float* y_mean, const float* y_std, float* out_lse,
+                                             double* out_sum, double* workspace, void* stream);
 
 /*
  * Multi-GPU (one process per GPU, batch sharded over ranks).  The communicator

@@ -5,8 +5,10 @@ Layout:
   csrc/                  HIP kernels for gfx950 + the extern "C" ABI (include/nfn.h):
                          nfn_persistent / nfn_group / nfn_tile (forward, posterior),
                          nfn_grad (fused backward), nfn_misc (reductions),
-                         nfn_mixture (kernel mixture log_prob, forward + backward),
-                         nfn_gmm (mixture density network log_prob, forward + backward),
+                         nfn_mixture (kernel mixture log_prob, forward + backward, and its
+                         posterior score over weight draws),
+                         nfn_gmm (mixture density network log_prob, forward + backward, and
+                         its posterior score over weight draws),
                          nfn_comm (RCCL all-reduce), nfn_api (validation + dispatch)
   build.py               parallel hipcc build of libnfn_hip.so (in-tree)
   _lib.py                ctypes binding of libnfn_hip.so (no CPU fallback)
@@ -14,8 +16,10 @@ Layout:
                          differentiable log_prob (autograd through the fused backward)
   normalizing_flows/     PlanarFlow / RadialFlow / AffineFlow, FLOWS, Chain, Invert
   distribution_layers.py InverseNormalizingFlowLayer and its flow distribution
-  estimators.py          NormalizingFlowNetwork (fit / pdf / log_pdf / score) and
-                         BayesNormalizingFlowNetwork (posterior score)
+  estimators.py          NormalizingFlowNetwork, KernelMixtureNetwork, MixtureDensityNetwork
+                         (fit / pdf / log_pdf / score) and, over BayesianNNEstimator,
+                         BayesNormalizingFlowNetwork, BayesMixtureDensityNetwork and
+                         BayesKernelMixtureNetwork (fused posterior score)
   scorers.py             mle / bayesian log-likelihood scorers
   parallel.py            batch-sharded multi-GPU mean log-likelihood (RCCL all-reduce)
 """
@@ -23,7 +27,8 @@ Layout:
 from .distribution_layers import (FlowDistribution, GaussianKernelsLayer, GaussianMixtureDistribution,
                                   GaussianMixtureLayer, InverseNormalizingFlowLayer, KernelMixtureDistribution,
                                   TensorShape)
-from .estimators import (BayesNormalizingFlowNetwork, KernelMixtureNetwork, MixtureDensityNetwork,
+from .estimators import (BayesianNNEstimator, BayesKernelMixtureNetwork, BayesMixtureDensityNetwork,
+                         BayesNormalizingFlowNetwork, KernelMixtureNetwork, MixtureDensityNetwork,
                          NormalizingFlowNetwork)
 from .normalizing_flows import FLOWS, AffineFlow, Bijector, Chain, Invert, PlanarFlow, RadialFlow
 
@@ -48,4 +53,7 @@ __all__ = [
     "GaussianMixtureLayer",
     "GaussianMixtureDistribution",
     "MixtureDensityNetwork",
+    "BayesianNNEstimator",
+    "BayesMixtureDensityNetwork",
+    "BayesKernelMixtureNetwork",
 ]

@@ -104,6 +104,18 @@ SIGNATURES = {
         _c_int32,
         [_vp, _c_int64, _vp, _c_int64, _c_int64, _c_int32, _c_int32, _vp, _vp, _vp, _vp, _vp, _c_int64, _vp, _vp],
     ),
+    "nfn_posterior_gaussian_mixture_workspace_doubles": (_c_int64, [_c_int64, _c_int32, _c_int32]),
+    "nfn_posterior_lse_gaussian_mixture_f32": (
+        _c_int32,
+        [_vp, _c_int64, _vp, _c_int64, _c_int64, _c_int32, _c_int64, _c_int32, _c_int32, _vp, _vp, _vp, _vp, _vp,
+         _vp],
+    ),
+    "nfn_posterior_kernel_mixture_workspace_doubles": (_c_int64, [_c_int64, _c_int32, _c_int32]),
+    "nfn_posterior_lse_kernel_mixture_f32": (
+        _c_int32,
+        [_vp, _c_int64, _vp, _c_int64, _c_int64, _c_int32, _vp, _vp, _c_int64, _c_int32, _c_int32, _vp, _vp, _vp,
+         _vp, _vp, _vp],
+    ),
     "nfn_comm_unique_id": (_c_int32, [_vp]),
     "nfn_comm_init": (_c_int32, [ctypes.POINTER(_vp), _c_int32, _vp, _c_int32]),
     "nfn_comm_destroy": (_c_int32, [_vp]),

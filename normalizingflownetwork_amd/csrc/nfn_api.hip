@@ -812,14 +812,21 @@ int32_t run_grid(const float* y_grid, int64_t y_gstride, int32_t G, const float*
   return check_hip("chain_grid_kernel launch");
 }
 
+// The draws of a mixture posterior entry: S rows per sample, draw s at s * stride floats.
+// NULL for the single-draw entries.
+struct Draws {
+  int64_t stride;
+  int32_t S;
+};
+
 // Gaussian-kernel mixture (nfn_mixture.hip).  The persistent grid never exceeds
 // kMixMaxParts workgroups, and a tile holds at least 4 rows: ONE function sizes both
 // workspaces and caps every launch.
 constexpr int64_t kMixMaxParts = 2048;
 int64_t mixture_parts(int64_t B) { return std::max<int64_t>(1, std::min<int64_t>(kMixMaxParts, (B + 3) / 4)); }
 
-int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* logits, int64_t logits_rowstride,
-                    const float* locs, const float* scales, int64_t B, int32_t d, int32_t M, const float* y_mean,
+int32_t run_mixture(bool grad, const Draws* draws, const float* y, int64_t y_bstride, const float* logits,
+                    int64_t logits_rowstride, const float* locs, const float* scales, int64_t B, int32_t d, int32_t M, const float* y_mean,
                     const float* y_std, const float* g_out, float* out_logp, double* out_sum, double* workspace,
                     float* grad_logits, int64_t grad_logits_rowstride, float* grad_y, float* grad_scales,
                     float* grad_workspace, void* stream) {
@@ -831,6 +838,8 @@ int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* l
   if (B < 0) return fail(NFN_E_SHAPE, "batch size must be >= 0");
   if (y_bstride < 0 || (y_bstride != 0 && y_bstride < d)) return fail(NFN_E_SHAPE, "bad y batch stride");
   if (logits_rowstride < M) return fail(NFN_E_SHAPE, "logits row stride < M");
+  if (draws && draws->S < 1) return fail(NFN_E_SHAPE, "number of draws must be >= 1");
+  if (draws && draws->stride < 0) return fail(NFN_E_SHAPE, "strides must be >= 0");
   if (grad && grad_logits && grad_logits_rowstride < M) return fail(NFN_E_SHAPE, "grad_logits row stride < M");
   if ((y_mean == nullptr) != (y_std == nullptr)) return fail(NFN_E_NULLPTR, "y_mean and y_std must both be given or both NULL");
   if (!y || !logits || !locs || !scales) return fail(NFN_E_NULLPTR, "y, logits, locs or scales is NULL");
@@ -858,6 +867,10 @@ int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* l
   a.d = d;
   a.M = M;
   a.grid_cap = mixture_parts(B);
+  if (draws) {
+    a.ds = draws->stride;
+    a.nd = draws->S;
+  }
   if (grad) {
     a.grad_logits = grad_logits;
     a.gl_rs = grad_logits ? grad_logits_rowstride : 0;
@@ -869,9 +882,13 @@ int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* l
     a.epoch = out_sum ? next_epoch() : 0u;
   }
   const size_t lds = sizeof(float) * ((size_t)3 * M + (size_t)M * d);
-  const int64_t grid = use_fast_math() ? launch_mixture_fast(grad, a, lds, s) : launch_mixture_precise(grad, a, lds, s);
+  int64_t grid;
+  if (draws)
+    grid = use_fast_math() ? launch_mixture_posterior_fast(a, lds, s) : launch_mixture_posterior_precise(a, lds, s);
+  else
+    grid = use_fast_math() ? launch_mixture_fast(grad, a, lds, s) : launch_mixture_precise(grad, a, lds, s);
   if (grid <= 0) return fail(NFN_E_SHAPE, "no kernel mixture instance for this shape");
-  int32_t rc = check_hip("kernel_mixture_kernel launch");
+  int32_t rc = check_hip(draws ? "kernel_mixture_posterior_kernel launch" : "kernel_mixture_kernel launch");
   if (rc == NFN_OK && grad && grad_scales) {
     launch_sum_partials(a.part, grid, M, grad_scales, nullptr, M, s);
     rc = check_hip("sum_partials_kernel launch");
@@ -885,8 +902,8 @@ int32_t run_mixture(bool grad, const float* y, int64_t y_bstride, const float* l
 constexpr int64_t kGmmMaxParts = 2048;
 int64_t gmm_parts(int64_t B) { return std::max<int64_t>(1, std::min<int64_t>(kGmmMaxParts, (B + 15) / 16)); }
 
-int32_t run_gmm(bool grad, const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride, int64_t B,
-                int32_t d, int32_t K, const float* y_mean, const float* y_std, const float* g_out, float* out_logp,
+int32_t run_gmm(bool grad, const Draws* draws, const float* y, int64_t y_bstride, const float* t,
+                int64_t t_rowstride, int64_t B, int32_t d, int32_t K, const float* y_mean, const float* y_std, const float* g_out, float* out_logp,
                 double* out_sum, double* workspace, float* grad_t, int64_t grad_t_rowstride, float* grad_y,
                 void* stream) {
   g_last_error.clear();
@@ -898,6 +915,8 @@ int32_t run_gmm(bool grad, const float* y, int64_t y_bstride, const float* t, in
   if (B < 0) return fail(NFN_E_SHAPE, "batch size must be >= 0");
   if (y_bstride < 0 || (y_bstride != 0 && y_bstride < d)) return fail(NFN_E_SHAPE, "bad y batch stride");
   if (t_rowstride < P) return fail(NFN_E_SHAPE, "t row stride < K * (2 * n_dims + 1)");
+  if (draws && draws->S < 1) return fail(NFN_E_SHAPE, "number of draws must be >= 1");
+  if (draws && draws->stride < 0) return fail(NFN_E_SHAPE, "strides must be >= 0");
   if (grad && grad_t && grad_t_rowstride < P) return fail(NFN_E_SHAPE, "grad_t row stride < K * (2 * n_dims + 1)");
   if ((y_mean == nullptr) != (y_std == nullptr)) return fail(NFN_E_NULLPTR, "y_mean and y_std must both be given or both NULL");
   if (!y || !t) return fail(NFN_E_NULLPTR, "y or t is NULL");
@@ -922,6 +941,10 @@ int32_t run_gmm(bool grad, const float* y, int64_t y_bstride, const float* t, in
   a.K = K;
   a.P = (int32_t)P;
   a.grid_cap = gmm_parts(B);
+  if (draws) {
+    a.ds = draws->stride;
+    a.nd = draws->S;
+  }
   if (grad) {
     a.grad_t = grad_t;
     a.gt_rs = grad_t ? grad_t_rowstride : 0;
@@ -931,9 +954,13 @@ int32_t run_gmm(bool grad, const float* y, int64_t y_bstride, const float* t, in
     a.out_sum = out_sum;
     a.epoch = out_sum ? next_epoch() : 0u;
   }
-  const int64_t grid = use_fast_math() ? launch_gmm_fast(grad, a, s) : launch_gmm_precise(grad, a, s);
+  int64_t grid;
+  if (draws)
+    grid = use_fast_math() ? launch_gmm_posterior_fast(a, s) : launch_gmm_posterior_precise(a, s);
+  else
+    grid = use_fast_math() ? launch_gmm_fast(grad, a, s) : launch_gmm_precise(grad, a, s);
   if (grid <= 0) return fail(NFN_E_SHAPE, "no Gaussian mixture launch for this shape");
-  return check_hip("gaussian_mixture_kernel launch");
+  return check_hip(draws ? "gaussian_mixture_posterior_kernel launch" : "gaussian_mixture_kernel launch");
 }
 
 }  // namespace
@@ -1059,8 +1086,8 @@ int32_t nfn_kernel_mixture_logprob_f32(const float* y, int64_t y_bstride, const 
                                        int64_t logits_rowstride, const float* locs, const float* scales, int64_t B,
                                        int32_t d, int32_t M, const float* y_mean, const float* y_std,
                                        float* out_logp, double* out_sum, double* workspace, void* stream) {
-  return run_mixture(false, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std, nullptr,
-                     out_logp, out_sum, workspace, nullptr, 0, nullptr, nullptr, nullptr, stream);
+  return run_mixture(false, nullptr, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std,
+                     nullptr, out_logp, out_sum, workspace, nullptr, 0, nullptr, nullptr, nullptr, stream);
 }
 
 int64_t nfn_kernel_mixture_grad_workspace_floats(int64_t B, int32_t d, int32_t M) {
@@ -1075,8 +1102,8 @@ int32_t nfn_kernel_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, c
                                             const float* g_out, float* out_logp, float* grad_logits,
                                             int64_t grad_logits_rowstride, float* grad_y, float* grad_scales,
                                             float* workspace, void* stream) {
-  return run_mixture(true, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std, g_out,
-                     out_logp, nullptr, nullptr, grad_logits, grad_logits_rowstride, grad_y, grad_scales, workspace,
+  return run_mixture(true, nullptr, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std,
+                     g_out, out_logp, nullptr, nullptr, grad_logits, grad_logits_rowstride, grad_y, grad_scales, workspace,
                      stream);
 }
 
@@ -1090,16 +1117,43 @@ int64_t nfn_gaussian_mixture_workspace_doubles(int64_t B, int32_t d, int32_t K) 
 int32_t nfn_gaussian_mixture_logprob_f32(const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride,
                                          int64_t B, int32_t d, int32_t K, const float* y_mean, const float* y_std,
                                          float* out_logp, double* out_sum, double* workspace, void* stream) {
-  return run_gmm(false, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, nullptr, out_logp, out_sum, workspace,
-                 nullptr, 0, nullptr, stream);
+  return run_gmm(false, nullptr, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, nullptr, out_logp, out_sum,
+                 workspace, nullptr, 0, nullptr, stream);
 }
 
 int32_t nfn_gaussian_mixture_logprob_grad_f32(const float* y, int64_t y_bstride, const float* t, int64_t t_rowstride,
                                               int64_t B, int32_t d, int32_t K, const float* y_mean,
                                               const float* y_std, const float* g_out, float* out_logp, float* grad_t,
                                               int64_t grad_t_rowstride, float* grad_y, void* stream) {
-  return run_gmm(true, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, g_out, out_logp, nullptr, nullptr,
-                 grad_t, grad_t_rowstride, grad_y, stream);
+  return run_gmm(true, nullptr, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, g_out, out_logp, nullptr,
+                 nullptr, grad_t, grad_t_rowstride, grad_y, stream);
+}
+
+int64_t nfn_posterior_gaussian_mixture_workspace_doubles(int64_t B, int32_t d, int32_t K) {
+  return nfn_gaussian_mixture_workspace_doubles(B, d, K);  // the same tiles and grid cap
+}
+
+int32_t nfn_posterior_lse_gaussian_mixture_f32(const float* y, int64_t y_bstride, const float* t,
+                                               int64_t t_drawstride, int64_t t_rowstride, int32_t S, int64_t B,
+                                               int32_t d, int32_t K, const float* y_mean, const float* y_std,
+                                               float* out_lse, double* out_sum, double* workspace, void* stream) {
+  const Draws draws = {t_drawstride, S};
+  return run_gmm(false, &draws, y, y_bstride, t, t_rowstride, B, d, K, y_mean, y_std, nullptr, out_lse, out_sum,
+                 workspace, nullptr, 0, nullptr, stream);
+}
+
+int64_t nfn_posterior_kernel_mixture_workspace_doubles(int64_t B, int32_t d, int32_t M) {
+  return nfn_kernel_mixture_workspace_doubles(B, d, M);  // the same tiles and grid cap
+}
+
+int32_t nfn_posterior_lse_kernel_mixture_f32(const float* y, int64_t y_bstride, const float* logits,
+                                             int64_t logits_drawstride, int64_t logits_rowstride, int32_t S,
+                                             const float* locs, const float* scales, int64_t B, int32_t d, int32_t M,
+                                             const float* y_mean, const float* y_std, float* out_lse,
+                                             double* out_sum, double* workspace, void* stream) {
+  const Draws draws = {logits_drawstride, S};
+  return run_mixture(false, &draws, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std,
+                     nullptr, out_lse, out_sum, workspace, nullptr, 0, nullptr, nullptr, nullptr, stream);
 }
 
 int32_t nfn_posterior_lse_dense_f32(const float* y, int64_t y_bstride, const float* h, int64_t h_drawstride,

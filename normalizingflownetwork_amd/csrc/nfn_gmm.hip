@@ -289,27 +289,108 @@ __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_kernel(GmmArgs a) 
   }
 }
 
-template <bool GRAD>
-int64_t launch_gmm(const GmmArgs& a0, hipStream_t s) {
-  GmmArgs a = a0;
+// The posterior score (BayesianNNEstimator.score, BayesianNNEstimator.py:65-76) of the same
+// layer: logsumexp over a.nd draws of the row's log_prob, minus log S.  The layout of
+// gaussian_mixture_kernel: a tile's y is staged and normalised once, then draw after draw
+// the tile's rows are staged and every lane pushes its gmm_row into its own running (m, acc)
+// (lse_push / lse_finish, nfn_device.h).  One float per sample leaves the kernel.
+template <bool FAST>
+__global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_posterior_kernel(GmmArgs a) {
+  extern __shared__ float lds[];
+  __shared__ double red[2 * kMaxBlock / 64];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int K = a.K, d = a.d, P = a.P, S = a.S, Sy = a.Sy, R = a.R;
+  float* tl = lds + wid * (R * (S + Sy));  // this wave's rows of t, then its rows of y
+  float* yl = tl + R * S;
+  float* row = tl + lane * S;
+  float* ys = yl + lane * Sy;
+  const WaveWalk wt = make_walk(a.vec4 ? P >> 2 : P, lane);
+  const WaveWalk wy = make_walk(d, lane);
+  float corr = 0.0f;
+  if (a.y_mean) {
+    for (int j = 0; j < d; ++j) corr += f_log<FAST>(a.y_std[j]);
+  }
+  double acc_sum = 0.0;
+  int nfc = 0;
+  for (int64_t tile = (int64_t)blockIdx.x * nw + wid; tile < a.ntiles; tile += (int64_t)gridDim.x * nw) {
+    const int64_t b0 = tile * R;
+    const int nr = (int)min((int64_t)R, a.B - b0);
+    wave_stage<false>(yl, a.y + b0 * a.y_bstride, a.y_bstride, nr, Sy, wy, lane);
+    wave_lds_sync();
+    if (lane < nr && a.y_mean) {
+      for (int j = 0; j < d; ++j) ys[j] = f_div_acc<FAST>(ys[j] - a.y_mean[j], a.y_std[j]);
+    }
+    float m = -INFINITY, lacc = 0.0f;
+    for (int s = 0; s < a.nd; ++s) {
+      const float* src = a.t + (int64_t)s * a.ds + b0 * a.rs;
+      if (a.vec4)
+        wave_stage<true>(tl, src, a.rs, nr, S, wt, lane);
+      else
+        wave_stage<false>(tl, src, a.rs, nr, S, wt, lane);
+      wave_lds_sync();
+      if (lane < nr) {
+        float ml, s0, acc;
+        double M;
+        float lp = gmm_row<FAST>(row, ys, K, d, ml, s0, M, acc) - corr;
+        // every logit -inf (s0 is exactly 0 then, and only then): the draw has no component
+        // left, its term is -inf and drops out (the single-draw entry gives NaN, -inf - -inf)
+        lp = s0 == 0.0f ? -INFINITY : lp;
+        lse_push<FAST>(m, lacc, lp);
+      }
+      wave_lds_sync();  // this draw's LDS reads are done before the next draw (or tile) is staged
+    }
+    if (lane < nr) {
+      const float res = lse_finish<FAST>(m, lacc, a.nd);
+      if (a.out) a.out[b0 + lane] = res;
+      acc_sum += (double)res;
+      nfc += nonfinite1(res);
+    }
+  }
+  if (a.partials) write_partial(a.partials, acc_sum, nfc, red, a.out_sum, a.epoch);
+}
+
+// Tile geometry of a launch: the LDS strides, the rows per wave tile and the tile count into
+// `a`; returns the waves per workgroup (0: the shape has no launch) and the LDS bytes.
+int gmm_geometry(GmmArgs& a, size_t& lds) {
   a.S = a.P | 1;
   a.Sy = a.d | 1;
   // rows per wave tile: 64 while 64 rows of P | 1 floats fit 64 KB, then 32, then 16 (P <= 1023)
   a.R = a.S <= 255 ? 64 : (a.S <= 511 ? 32 : 16);
   const size_t wave_bytes = sizeof(float) * (size_t)a.R * (size_t)(a.S + a.Sy);
   const int waves = (int)std::max<size_t>(1, std::min<size_t>(kMaxBlock / 64, kGmmLdsBudget / wave_bytes));
-  const size_t lds = wave_bytes * waves;
+  lds = wave_bytes * waves;
   if (lds > (size_t)kLdsMaxBytes) return 0;
   // the 16-byte path only where the rows allow it (P is odd whenever K is: dwords are the rule)
   const bool v4 = (a.P & 3) == 0;
-  a.vec4 = v4 && (a.rs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.t) & 15) == 0;
-  a.gt_vec4 = a.vec4 && a.grad_t && (a.gt_rs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.grad_t) & 15) == 0;
+  a.vec4 = v4 && (a.rs & 3) == 0 && (a.ds & 3) == 0 && (reinterpret_cast<uintptr_t>(a.t) & 15) == 0;
   a.ntiles = (a.B + a.R - 1) / a.R;
-  auto kfn = gaussian_mixture_kernel<kFast, GRAD>;
+  return waves;
+}
+
+template <typename KFN>
+int64_t launch_gmm_kernel(KFN kfn, const GmmArgs& a, int waves, size_t lds, hipStream_t s) {
   int64_t grid = persistent_grid(kfn, 64 * waves, lds, (a.ntiles + waves - 1) / waves);
   grid = std::max<int64_t>(1, std::min(grid, a.grid_cap));
   nfn_launch(kfn, dim3((unsigned)grid), dim3((unsigned)(64 * waves)), (uint32_t)lds, s, a);
   return grid;
+}
+
+template <bool GRAD>
+int64_t launch_gmm(const GmmArgs& a0, hipStream_t s) {
+  GmmArgs a = a0;
+  size_t lds;
+  const int waves = gmm_geometry(a, lds);
+  if (waves == 0) return 0;
+  a.gt_vec4 = a.vec4 && a.grad_t && (a.gt_rs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.grad_t) & 15) == 0;
+  return launch_gmm_kernel(gaussian_mixture_kernel<kFast, GRAD>, a, waves, lds, s);
+}
+
+int64_t launch_gmm_posterior(const GmmArgs& a0, hipStream_t s) {
+  GmmArgs a = a0;
+  size_t lds;
+  const int waves = gmm_geometry(a, lds);
+  if (waves == 0) return 0;
+  return launch_gmm_kernel(gaussian_mixture_posterior_kernel<kFast>, a, waves, lds, s);
 }
 
 }  // namespace
@@ -321,5 +402,11 @@ int64_t launch_gmm_precise(bool grad, const GmmArgs& a, hipStream_t s) {
 #endif
   return grad ? launch_gmm<true>(a, s) : launch_gmm<false>(a, s);
 }
+
+#if NFN_FAST
+int64_t launch_gmm_posterior_fast(const GmmArgs& a, hipStream_t s) { return launch_gmm_posterior(a, s); }
+#else
+int64_t launch_gmm_posterior_precise(const GmmArgs& a, hipStream_t s) { return launch_gmm_posterior(a, s); }
+#endif
 
 }  // namespace nfn

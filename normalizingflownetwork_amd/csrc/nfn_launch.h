@@ -231,10 +231,16 @@ struct MixArgs {
   int32_t d;
   int32_t M;
   uint32_t epoch;
+  int64_t ds;            // posterior: draw stride of the logits (floats)
+  int32_t nd;            // posterior: number of draws S
 };
 // launches the (G, NV) instance for M; returns the grid (= number of partials written)
 int64_t launch_mixture_fast(bool grad, const MixArgs& a, size_t lds, hipStream_t s);
 int64_t launch_mixture_precise(bool grad, const MixArgs& a, size_t lds, hipStream_t s);
+// the posterior score over a.nd draws (nfn_posterior_lse_kernel_mixture_f32): a.out is the
+// per-sample logsumexp over draws - log S
+int64_t launch_mixture_posterior_fast(const MixArgs& a, size_t lds, hipStream_t s);
+int64_t launch_mixture_posterior_precise(const MixArgs& a, size_t lds, hipStream_t s);
 // nfn_gmm.hip (compiled once per math mode): the mixture density network's Gaussian-mixture
 // log_prob (nfn_gaussian_mixture_logprob_f32) and its backward
 struct GmmArgs {
@@ -263,10 +269,16 @@ struct GmmArgs {
   int32_t vec4;          // set by the launcher: t rows can be streamed as float4
   int32_t gt_vec4;       // set by the launcher: grad_t rows can be written as float4
   uint32_t epoch;
+  int64_t ds;            // posterior: draw stride of t (floats)
+  int32_t nd;            // posterior: number of draws S
 };
 // returns the grid (= number of partials written); 0 if the shape has no launch
 int64_t launch_gmm_fast(bool grad, const GmmArgs& a, hipStream_t s);
 int64_t launch_gmm_precise(bool grad, const GmmArgs& a, hipStream_t s);
+// the posterior score over a.nd draws (nfn_posterior_lse_gaussian_mixture_f32): a.out is the
+// per-sample logsumexp over draws - log S
+int64_t launch_gmm_posterior_fast(const GmmArgs& a, hipStream_t s);
+int64_t launch_gmm_posterior_precise(const GmmArgs& a, hipStream_t s);
 // nfn_sample.hip
 void launch_sample(bool fast, int dm, const SampleArgs& sa, dim3 grid, dim3 block, size_t lds, hipStream_t s);
 // nfn_grid.hip

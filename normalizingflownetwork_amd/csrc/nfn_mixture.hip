@@ -223,6 +223,187 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
   }
 }
 
+// The posterior score (BayesianNNEstimator.score, BayesianNNEstimator.py:65-76) of the same
+// layer: logsumexp over a.nd draws of the row's log_prob, minus log S.  The (G, NV) groups
+// and the tiles of kernel_mixture_kernel.  c_bk depends on y_b and the centres only, so a
+// row's NV values per lane are formed once and kept in registers; per draw only the NV
+// logits are loaded, and the next draw's loads are issued before this draw's reductions.
+// Each draw's log_prob is evaluated as the forward evaluates it, operation for operation.
+template <int G, int NV, bool FAST>
+__global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(MixArgs a) {
+  extern __shared__ float lds[];
+  __shared__ double red[2 * kMaxBlock / 64];
+  constexpr int GPB = kMaxBlock / G;  // groups per workgroup
+  constexpr int RPG = mix_rpg(NV);
+  constexpr int ROWS = GPB * RPG;
+  const int M = a.M, d = a.d, S = a.nd;
+  const int tid = threadIdx.x;
+  float* inv_s2 = lds;
+  float* lcs = lds + M;
+  float* locT = lds + 3 * M;
+  for (int k = tid; k < M; k += kMaxBlock) {
+    const double s = (double)a.scales[k];
+    inv_s2[k] = (float)(1.0 / (s * s));
+    lcs[k] = (float)(-(double)d * (log(fabs(s)) + 0.91893853320467274));
+  }
+  for (int i = tid; i < M * d; i += kMaxBlock) {
+    const int k = i / d, j = i - k * d;
+    locT[j * M + k] = a.locs[i];
+  }
+  __syncthreads();
+  float corr = 0.0f;
+  if (a.y_mean) {
+    for (int j = 0; j < d; ++j) corr += f_log<FAST>(a.y_std[j]);
+  }
+  const int lg = tid & (G - 1), grp = tid / G;
+  int kk[NV];
+  bool act[NV];
+  float is2[NV], lc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int k = lg + G * i;
+    act[i] = k < M;
+    kk[i] = act[i] ? k : 0;
+    is2[i] = inv_s2[kk[i]];
+    lc[i] = lcs[kk[i]];
+  }
+  double acc = 0.0;
+  int nfc = 0;
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const int64_t b0 = tile * ROWS + grp;
+    // The next draw's logits, in flight.  Every load is unconditional, from a clamped address
+    // (row 0 past B, column 0 past M), and masked when it is consumed: a load under a per-lane
+    // condition is waited for where its branch joins, one memory latency after the other.
+    float nx[RPG][NV];
+    const float* tr[RPG];
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) {
+      const int64_t b = b0 + (int64_t)r * GPB;
+      tr[r] = a.logits + (b < a.B ? b : 0) * a.rs;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) nx[r][i] = __builtin_nontemporal_load(tr[r] + kk[i]);
+    }
+    // the S-independent part: c_k of every row of the tile
+    float cv[RPG][NV];
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) {
+      const int64_t b = b0 + (int64_t)r * GPB;
+      const float* yr = a.y + (b < a.B ? b * a.y_bstride : 0);
+      float z2[NV];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) z2[i] = 0.0f;
+      for (int j = 0; j < d; ++j) {
+        float yj = yr[j];
+        if (a.y_mean) yj = f_div<FAST>(yj - a.y_mean[j], a.y_std[j]);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          const float dy = yj - locT[j * M + kk[i]];
+          z2[i] = fmaf(dy, dy, z2[i]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        z2[i] *= is2[i];
+        cv[r][i] = fmaf(-0.5f, z2[i], lc[i]);
+      }
+    }
+    float m[RPG], la[RPG];
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) {
+      m[r] = -INFINITY;
+      la[r] = 0.0f;
+    }
+    for (int s = 0; s < S; ++s) {
+      float tv[RPG][NV];
+#pragma unroll
+      for (int r = 0; r < RPG; ++r) {
+        const bool ok = b0 + (int64_t)r * GPB < a.B;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) tv[r][i] = (ok && act[i]) ? nx[r][i] : -INFINITY;
+      }
+      if (s + 1 < S) {
+#pragma unroll
+        for (int r = 0; r < RPG; ++r) {
+          const float* tn = tr[r] + (int64_t)(s + 1) * a.ds;
+#pragma unroll
+          for (int i = 0; i < NV; ++i) nx[r][i] = __builtin_nontemporal_load(tn + kk[i]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < RPG; ++r) {
+        float mt = tv[r][0];
+#pragma unroll
+        for (int i = 1; i < NV; ++i) mt = fmaxf(mt, tv[r][i]);
+        mt = mix_gmax<G>(mt);
+        float av[NV], e0[NV];
+        float ma = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          // a lane past M and a -inf logit contribute exactly nothing (no -inf - -inf)
+          const float u = tv[r][i] == -INFINITY ? -INFINITY : tv[r][i] - mt;
+          e0[i] = f_exp<FAST>(u);
+          av[i] = u + cv[r][i];
+          ma = fmaxf(ma, av[i]);
+        }
+        ma = mix_gmax<G>(ma);
+        float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          s0 += e0[i];
+          s1 += av[i] == -INFINITY ? 0.0f : f_exp<FAST>(av[i] - ma);
+        }
+        s0 = mix_gsum<G>(s0);
+        s1 = mix_gsum<G>(s1);
+        float lp = (ma + f_log<FAST>(s1)) - f_log<FAST>(s0) - corr;
+        // every logit -inf (s0 is exactly 0 then, and only then): the draw has no component
+        // left, its term is -inf and drops out (the single-draw entry gives NaN, -inf - -inf)
+        lp = s0 == 0.0f ? -INFINITY : lp;
+        lse_push<FAST>(m[r], la[r], lp);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RPG; ++r) {
+      const int64_t b = b0 + (int64_t)r * GPB;
+      if (b < a.B && lg == 0) {
+        const float res = lse_finish<FAST>(m[r], la[r], S);
+        if (a.out) a.out[b] = res;
+        acc += (double)res;
+        nfc += nonfinite1(res);
+      }
+    }
+  }
+  if (a.partials) write_partial(a.partials, acc, nfc, red, a.out_sum, a.epoch);
+}
+
+template <int G, int NV>
+int64_t launch_posterior_one(const MixArgs& a0, size_t lds, hipStream_t s) {
+  MixArgs a = a0;
+  constexpr int ROWS = (kMaxBlock / G) * mix_rpg(NV);
+  a.ntiles = (a.B + ROWS - 1) / ROWS;
+  auto kfn = kernel_mixture_posterior_kernel<G, NV, kFast>;
+  int64_t grid = persistent_grid(kfn, kMaxBlock, lds, a.ntiles);
+  grid = std::max<int64_t>(1, std::min(grid, a.grid_cap));
+  nfn_launch(kfn, dim3((unsigned)grid), dim3(kMaxBlock), (uint32_t)lds, s, a);
+  return grid;
+}
+
+// the (G, NV) instance of launch_shape
+int64_t launch_posterior_shape(const MixArgs& a, size_t lds, hipStream_t s) {
+  const int M = a.M;
+  if (M <= 1) return launch_posterior_one<1, 1>(a, lds, s);
+  if (M <= 2) return launch_posterior_one<2, 1>(a, lds, s);
+  if (M <= 4) return launch_posterior_one<4, 1>(a, lds, s);
+  if (M <= 8) return launch_posterior_one<8, 1>(a, lds, s);
+  if (M <= 16) return launch_posterior_one<16, 1>(a, lds, s);
+  if (M <= 32) return launch_posterior_one<16, 2>(a, lds, s);
+  if (M <= 64) return launch_posterior_one<16, 4>(a, lds, s);
+  if (M <= 128) return launch_posterior_one<16, 8>(a, lds, s);
+  if (M <= 256) return launch_posterior_one<16, 16>(a, lds, s);
+  if (M <= 512) return launch_posterior_one<32, 16>(a, lds, s);
+  if (M <= 1024) return launch_posterior_one<64, 16>(a, lds, s);
+  return 0;
+}
+
 template <int G, int NV, bool GRAD>
 int64_t launch_one(const MixArgs& a0, size_t lds, hipStream_t s) {
   MixArgs a = a0;
@@ -264,6 +445,14 @@ int64_t launch_mixture_fast(bool grad, const MixArgs& a, size_t lds, hipStream_t
 int64_t launch_mixture_precise(bool grad, const MixArgs& a, size_t lds, hipStream_t s) {
 #endif
   return grad ? launch_shape<true>(a, lds, s) : launch_shape<false>(a, lds, s);
+}
+
+#if NFN_FAST
+int64_t launch_mixture_posterior_fast(const MixArgs& a, size_t lds, hipStream_t s) {
+#else
+int64_t launch_mixture_posterior_precise(const MixArgs& a, size_t lds, hipStream_t s) {
+#endif
+  return launch_posterior_shape(a, lds, s);
 }
 
 }  // namespace nfn

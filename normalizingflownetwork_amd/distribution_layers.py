@@ -321,6 +321,12 @@ class InverseNormalizingFlowLayer:
     def finish_training(self) -> None:
         pass
 
+    def posterior_lse(self, y, t_draws, y_mean=None, y_std=None, **want):
+        """``logsumexp_s(log_pdf(y_b | t_draws[s, b])) - log S`` per sample, fused
+        (``BayesianNNEstimator.py:65-76``); ``want`` as for :func:`ops.posterior_lse`."""
+        return ops.posterior_lse(y, t_draws, self._flow_types, self._n_dims, self._trainable_base_dist, y_mean,
+                                 y_std, **want)
+
     @staticmethod
     def _get_bijector(t, flow_types, n_dims):
         """Chain of flows; blocks are split in REVERSED ``flow_types`` order and
@@ -476,6 +482,14 @@ class GaussianKernelsLayer:
     def finish_training(self) -> None:
         self.v = self.v.detach()
 
+    def posterior_lse(self, y, t_draws, y_mean=None, y_std=None, **want):
+        """``logsumexp_s(log_pdf(y_b | t_draws[s, b])) - log S`` per sample, fused
+        (``BayesianNNEstimator.py:65-76``); ``want`` as for :func:`ops.posterior_lse`."""
+        dev = ops._device()
+        with torch.no_grad():
+            return ops.posterior_lse_kernel_mixture(y, t_draws, self._device_locs(dev), self.scales(dev), y_mean,
+                                                    y_std, **want)
+
     def set_center_points(self, y, seed: int = 22):
         """``DistributionLayers.py:135-172``: ``n_edge = min(2 d, n_centers // 2)`` centres on
         the data's rim — among the ``2 n_edge`` points farthest from the mean, picked greedily
@@ -552,3 +566,8 @@ class GaussianMixtureLayer:
 
     def finish_training(self) -> None:
         pass
+
+    def posterior_lse(self, y, t_draws, y_mean=None, y_std=None, **want):
+        """``logsumexp_s(log_pdf(y_b | t_draws[s, b])) - log S`` per sample, fused
+        (``BayesianNNEstimator.py:65-76``); ``want`` as for :func:`ops.posterior_lse`."""
+        return ops.posterior_lse_gaussian_mixture(y, t_draws, self.n_centers, self.n_dims, y_mean, y_std, **want)

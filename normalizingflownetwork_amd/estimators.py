@@ -17,6 +17,11 @@ estimator's variational training (KL term) is not mirrored.
 dispatches through the density layer (its trainable tensors, its differentiable train-time
 ``log_prob``), so the same loop trains the flow chain or the kernel mixture.
 ``MixtureDensityNetwork`` (``estimators/MixtureDensityNetwork.py``) is the third such layer.
+
+``BayesianNNEstimator`` holds the posterior machinery (weight draws, ``params_draws``,
+``evaluate``, the chunked fused ``score``) for any of the three layers:
+``BayesNormalizingFlowNetwork`` (which keeps its fused-Dense ``score``),
+``BayesMixtureDensityNetwork`` and ``BayesKernelMixtureNetwork``.
 """
 
 from __future__ import annotations
@@ -482,29 +487,30 @@ def mean_field_scale(rho: torch.Tensor) -> torch.Tensor:
     return 1e-3 + torch.nn.functional.softplus(float(np.log(np.expm1(1.0))) + 0.05 * rho)
 
 
-class BayesNormalizingFlowNetwork(BaseEstimator):
-    """Posterior-scoring half of ``estimators/BayesNormalizingFlowNetwork.py`` /
-    ``BayesianNNEstimator.py``.  Every layer is a ``DenseVariational`` whose weights
+# score: the (S, rows, P) draws of one chunk stay at or under this many bytes (a fixed cap, not
+# a tuned number: S = 50 draws of a P = 100 row are 20 KB per sample)
+POSTERIOR_CHUNK_BYTES = 256 << 20
+
+
+class BayesianNNEstimator(BaseEstimator):
+    """Posterior-scoring half of ``estimators/BayesianNNEstimator.py`` for any density layer
+    (``dist_layer``: a flow chain, the Gaussian mixture or the kernel mixture).  Every layer
+    is a ``DenseVariational`` whose weights
     (kernel and bias) have a mean-field Gaussian posterior held as one variable vector
     ``[loc | rho]`` initialised N(0, 0.05) (Keras ``"normal"``; ``BayesianNNEstimator.py:92-107``,
     ``DistributionLayers.py:17-55``): a draw is ``loc + (1e-3 + softplus(log(e-1) + 0.05 rho))
     * eps``, one weight sample per layer per draw shared by the batch (``:122-145``); in
     ``map_mode`` the variable holds ``loc`` only and the weights ARE ``loc``.  ``score``
-    stacks the S draws' last hidden activations and output-layer weights and evaluates
-    ``logsumexp_s(log_pdf) - log S`` per sample in ONE fused kernel
-    (``nfn_posterior_lse_dense_f32``, the output DenseVariational layer fused; or
-    ``nfn_posterior_lse_f32`` over a library-GEMM ``t``) instead of S model re-runs.
+    forms ``t`` of the S draws with one batched GEMM and evaluates
+    ``logsumexp_s(log_pdf) - log S`` per sample in ONE fused kernel per row chunk (the
+    layer's ``posterior_lse``) instead of S model re-runs.
     ``fit`` trains the posterior means by maximum likelihood; the KL(q || p) term and
     the scales' training are not mirrored (out of scope)."""
 
-    def __init__(self, n_dims, kl_weight_scale=1.0, n_flows=2, trainable_base_dist=True, flow_types=None,
-                 hidden_sizes=(10,), activation="tanh", noise_reg=("fixed_rate", 0.0), learning_rate=2e-2,
-                 map_mode=False, prior_scale=1.0, trainable_prior=False, kl_use_exact=True, random_seed=22,
-                 n_dims_x=None):
+    def __init__(self, dist_layer, kl_weight_scale, kl_use_exact=True, hidden_sizes=(10,), activation="tanh",
+                 learning_rate=3e-2, noise_reg=("fixed_rate", 0.0), trainable_prior=False, map_mode=False,
+                 prior_scale=1.0, random_seed=22, n_dims_x=None):
         assert kl_weight_scale <= 1.0  # BayesianNNEstimator.py:120
-        flow_types = tuple(flow_types) if flow_types is not None else ("radial",) * n_flows
-        dist_layer = InverseNormalizingFlowLayer(flow_types=flow_types, n_dims=n_dims,
-                                                 trainable_base_dist=trainable_base_dist)
         self.map_mode = map_mode
         self.prior_scale = prior_scale
         self.trainable_prior = trainable_prior
@@ -592,6 +598,46 @@ class BayesNormalizingFlowNetwork(BaseEstimator):
         return torch.matmul(h, W) + b[:, None, :]
 
     def score(self, x_data, y_data, n_draws: Optional[int] = None) -> float:
+        """``BayesianNNEstimator.py:65-76``: 50 draws (1 in map mode).  The S networks are
+        drawn once; ``t`` of every draw is formed by the batched library GEMM and scored by the
+        layer's fused posterior kernel, in row chunks that keep the (S, rows, P) tensor at or
+        under ``POSTERIOR_CHUNK_BYTES``.  The chunks' {sum, non-finite count} pairs are added
+        in fp64 on the device."""
+        S = n_draws if n_draws is not None else (1 if self.map_mode else 50)
+        y = ops.as_device_f32(np.asarray(y_data, np.float32))
+        n = int(y.shape[0])
+        with torch.no_grad():
+            h, W, b = self._last_layer_draws(np.asarray(x_data, np.float32), S)
+            rows = max(1, POSTERIOR_CHUNK_BYTES // (4 * S * int(W.shape[-1])))
+            s = nf = None
+            for r0 in range(0, n, rows):
+                t = torch.matmul(h[:, r0:r0 + rows], W) + b[:, None, :]
+                _, cs, cnf = self.dist_layer.posterior_lse(y[r0:r0 + rows], t, self.y_mean, self.y_std,
+                                                           want_values=False, want_sum=True, want_nonfinite=True)
+                s, nf = (cs, cnf) if s is None else (s + cs, nf + cnf)
+        return self._finish_score(s, nf, n)
+
+
+class BayesNormalizingFlowNetwork(BayesianNNEstimator):
+    """``estimators/BayesNormalizingFlowNetwork.py`` over :class:`BayesianNNEstimator`.  ``score``
+    stacks the S draws' last hidden activations and output-layer weights and evaluates
+    ``logsumexp_s(log_pdf) - log S`` per sample in ONE fused kernel
+    (``nfn_posterior_lse_dense_f32``, the output DenseVariational layer fused; or
+    ``nfn_posterior_lse_f32`` over a library-GEMM ``t``) instead of S model re-runs."""
+
+    def __init__(self, n_dims, kl_weight_scale=1.0, n_flows=2, trainable_base_dist=True, flow_types=None,
+                 hidden_sizes=(10,), activation="tanh", noise_reg=("fixed_rate", 0.0), learning_rate=2e-2,
+                 map_mode=False, prior_scale=1.0, trainable_prior=False, kl_use_exact=True, random_seed=22,
+                 n_dims_x=None):
+        flow_types = tuple(flow_types) if flow_types is not None else ("radial",) * n_flows
+        dist_layer = InverseNormalizingFlowLayer(flow_types=flow_types, n_dims=n_dims,
+                                                 trainable_base_dist=trainable_base_dist)
+        super().__init__(dist_layer, kl_weight_scale, kl_use_exact=kl_use_exact, hidden_sizes=hidden_sizes,
+                         activation=activation, learning_rate=learning_rate, noise_reg=noise_reg,
+                         trainable_prior=trainable_prior, map_mode=map_mode, prior_scale=prior_scale,
+                         random_seed=random_seed, n_dims_x=n_dims_x)
+
+    def score(self, x_data, y_data, n_draws: Optional[int] = None) -> float:
         """``BayesianNNEstimator.py:65-76``: 50 draws (1 in map mode).  The output layer is
         fused into the posterior kernel (``nfn_posterior_lse_dense_f32``: t_s = h_s W_s + b_s
         never written to memory) when its width allows, else t is formed by the library GEMM."""
@@ -601,3 +647,56 @@ class BayesNormalizingFlowNetwork(BaseEstimator):
                                            self.n_dims, self.dist_layer.trainable_base_dist, self.y_mean,
                                            self.y_std, want_values=False, want_sum=True, want_nonfinite=True)
         return self._finish_score(s, nf, int(np.shape(y_data)[0]))
+
+
+class BayesMixtureDensityNetwork(BayesianNNEstimator):
+    """``estimators/BayesMixtureDensityNetwork.py``: the Bayesian net over a
+    ``GaussianMixtureLayer``.  ``score`` is the fused posterior kernel
+    ``nfn_posterior_lse_gaussian_mixture_f32``.  ``fit`` trains the posterior means by maximum
+    likelihood through the fused mixture backward; the KL(q || p) term and the scales'
+    training are not mirrored (out of scope)."""
+
+    def __init__(self, n_dims, kl_weight_scale, n_centers=5, **kwargs):
+        dist_layer = GaussianMixtureLayer(n_centers=n_centers, n_dims=n_dims)
+        super().__init__(dist_layer, kl_weight_scale, **kwargs)
+
+    @staticmethod
+    def build_function(n_dims, kl_weight_scale, n_centers=5, kl_use_exact=True, hidden_sizes=(10,),
+                       activation="tanh", noise_reg=("fixed_rate", 0.0), learning_rate=2e-2, trainable_prior=False,
+                       map_mode=False, prior_scale=1.0):
+        return BayesMixtureDensityNetwork(n_dims=n_dims, kl_weight_scale=kl_weight_scale, n_centers=n_centers,
+                                          kl_use_exact=kl_use_exact, hidden_sizes=hidden_sizes,
+                                          activation=activation, noise_reg=noise_reg, learning_rate=learning_rate,
+                                          trainable_prior=trainable_prior, map_mode=map_mode,
+                                          prior_scale=prior_scale)
+
+
+class BayesKernelMixtureNetwork(BayesianNNEstimator):
+    """``estimators/BayesKernelMixtureNetwork.py``: the Bayesian net over a
+    ``GaussianKernelsLayer``.  ``score`` is the fused posterior kernel
+    ``nfn_posterior_lse_kernel_mixture_f32``.  ``fit`` trains the posterior means (and the
+    layer's bandwidth variable) by maximum likelihood through the fused mixture backward; the
+    KL(q || p) term and the scales' training are not mirrored (out of scope)."""
+
+    def __init__(self, n_dims, kl_weight_scale, n_centers=50, **kwargs):
+        dist_layer = GaussianKernelsLayer(n_centers=n_centers, n_dims=n_dims, trainable_scale=True)
+        super().__init__(dist_layer, kl_weight_scale, **kwargs)
+
+    @staticmethod
+    def build_function(n_dims, kl_weight_scale, n_centers=50, kl_use_exact=True, hidden_sizes=(10,),
+                       activation="tanh", noise_reg=("fixed_rate", 0.0), learning_rate=2e-2, trainable_prior=False,
+                       map_mode=False, prior_scale=1.0):
+        return BayesKernelMixtureNetwork(n_dims=n_dims, kl_weight_scale=kl_weight_scale, n_centers=n_centers,
+                                         kl_use_exact=kl_use_exact, hidden_sizes=hidden_sizes,
+                                         activation=activation, noise_reg=noise_reg, learning_rate=learning_rate,
+                                         trainable_prior=trainable_prior, map_mode=map_mode,
+                                         prior_scale=prior_scale)
+
+    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, **kwargs):
+        """``BayesKernelMixtureNetwork.py:47-51``: the kernel centres are set from the normalised
+        targets, then the posterior means train as in ``BaseEstimator.fit``."""
+        y = np.asarray(y, np.float32)
+        y_mean = np.mean(y, axis=0, dtype=np.float32)
+        y_std = np.std(y, axis=0, dtype=np.float32)
+        self.dist_layer.set_center_points((y - y_mean) / y_std, seed=int(self.random_seed))
+        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)

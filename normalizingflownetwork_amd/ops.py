@@ -1280,3 +1280,73 @@ def gaussian_mixture_log_prob_diff(y, t, n_centers, n_dims, y_mean=None, y_std=N
     t = _prep_2d(t, K * (2 * d + 1), "t", dev)
     y_mean, y_std = _norm_stats(y_mean, y_std, d, dev)
     return _GaussianMixtureLogProb.apply(y, t, K, d, y_mean, y_std)
+
+
+# ---------------------------------------------------------------------------
+# Posterior scores of the two mixture layers (BayesianNNEstimator.score)
+# ---------------------------------------------------------------------------
+
+def _draw_inputs(y, draws, width: int, n_dims: int, y_mean, y_std, device, name: str):
+    """``(y, draws, draw stride, row stride, y_mean, y_std, S, B)`` of a mixture posterior
+    entry: ``draws`` (S, B, width) with a unit column stride, its draw and row strides taken
+    from the tensor (a column view or a row slice of a larger tensor stays a view); ``y``
+    (B or 1, d).  The ABI's rows do not broadcast and have a stride >= width: anything else
+    is materialised."""
+    y = _prep_2d(y, n_dims, "y", device)
+    draws = as_device_f32(draws, device)
+    assert draws.dim() == 3 and draws.shape[-1] == width, f"{name} must be (S, B, {width})"
+    S, Bt = int(draws.shape[0]), int(draws.shape[1])
+    assert S >= 1, "number of draws must be >= 1"
+    B = max(int(y.shape[0]), Bt)
+    assert y.shape[0] in (1, B) and Bt in (1, B), "incompatible batch sizes"
+    if Bt != B:
+        draws = draws.expand(S, B, width).contiguous()
+    if draws.stride(-1) != 1 or (B > 1 and draws.stride(1) < width):
+        draws = draws.contiguous()
+    ds = int(draws.stride(0)) if S > 1 else 0
+    rs = int(draws.stride(1)) if B > 1 else width
+    return (y, draws, ds, rs) + _norm_stats(y_mean, y_std, n_dims, device) + (S, B)
+
+
+def posterior_lse_gaussian_mixture(y, t_draws, n_centers, n_dims, y_mean=None, y_std=None, want_values: bool = True,
+                                   want_sum: bool = False, want_nonfinite: bool = False):
+    """``logsumexp_s(log_pdf(y_b | t[s, b])) - log S`` per sample under the mixture density
+    network's density (``BayesianNNEstimator.py:65-76`` over a ``GaussianMixtureLayer``), in
+    ONE fused kernel: ``y`` is read once, the running log-sum-exp stays in registers and one
+    float per sample is written.  ``t_draws``: (S, B, K (2 d + 1)).  A draw whose logits are all
+    ``-inf`` counts as a ``-inf`` term and drops out (include/nfn.h).  Returns as
+    :func:`posterior_lse`; not differentiable."""
+    dev = _device()
+    K, d = int(n_centers), int(n_dims)
+    y, t, ds, rs, ym, ys, S, B = _draw_inputs(y, t_draws, K * (2 * d + 1), d, y_mean, y_std, dev, "t_draws")
+    lib = _lib.load()
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite or not want_values,
+                                 lambda: lib.nfn_posterior_gaussian_mixture_workspace_doubles(B, d, K), dev)
+    rc = lib.nfn_posterior_lse_gaussian_mixture_f32(
+        _ptr(y), _row_stride(y), _ptr(t), ds, rs, S, B, d, K, _ptr(ym), _ptr(ys), _ptr(out), _ptr(osum), _ptr(ws),
+        _stream(),
+    )
+    _lib.check(rc, "nfn_posterior_lse_gaussian_mixture_f32")
+    return _with_nonfinite(out, osum, want_nonfinite)
+
+
+def posterior_lse_kernel_mixture(y, logits_draws, locs, scales, y_mean=None, y_std=None, want_values: bool = True,
+                                 want_sum: bool = False, want_nonfinite: bool = False):
+    """``logsumexp_s(log_pdf(y_b | logits[s, b])) - log S`` per sample under the kernel mixture
+    network's density (``BayesianNNEstimator.py:65-76`` over a ``GaussianKernelsLayer``), in
+    ONE fused kernel: the kernel terms ``c_bk`` (a function of ``y_b`` and the fixed centres
+    only) are formed once per row, not once per draw.  ``logits_draws``: (S, B, M).  A draw whose
+    logits are all ``-inf`` counts as a ``-inf`` term and drops out (include/nfn.h).  Returns as
+    :func:`posterior_lse`; not differentiable."""
+    dev = _device()
+    locs, scales, M, d = _kernel_params(locs, scales, dev)
+    y, lg, ds, rs, ym, ys, S, B = _draw_inputs(y, logits_draws, M, d, y_mean, y_std, dev, "logits_draws")
+    lib = _lib.load()
+    out, osum, ws = _sum_outputs(B, want_values, want_sum or want_nonfinite or not want_values,
+                                 lambda: lib.nfn_posterior_kernel_mixture_workspace_doubles(B, d, M), dev)
+    rc = lib.nfn_posterior_lse_kernel_mixture_f32(
+        _ptr(y), _row_stride(y), _ptr(lg), ds, rs, S, _ptr(locs), _ptr(scales), B, d, M, _ptr(ym), _ptr(ys),
+        _ptr(out), _ptr(osum), _ptr(ws), _stream(),
+    )
+    _lib.check(rc, "nfn_posterior_lse_kernel_mixture_f32")
+    return _with_nonfinite(out, osum, want_nonfinite)

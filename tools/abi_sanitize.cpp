@@ -127,6 +127,39 @@ int main() {
   EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, nullptr, 15, 10, 1, 5, nullptr, nullptr, nullptr, nullptr, f, 15, f, nullptr), NFN_E_NULLPTR);
   EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, f, 15, 10, 1, 5, nullptr, f, nullptr, nullptr, f, 15, f, nullptr), NFN_E_NULLPTR);
   EXPECT(nfn_gaussian_mixture_logprob_grad_f32(f, 1, f, 15, 0, 1, 5, nullptr, nullptr, nullptr, nullptr, f, 15, f, nullptr), NFN_OK);
+  // posterior scores of the two mixture layers: rejection paths, workspace sizes, B = 0
+  for (int64_t B : {(int64_t)0, (int64_t)1, (int64_t)1000, (int64_t)1 << 24, (int64_t)1 << 27}) {
+    EXPECT(nfn_posterior_gaussian_mixture_workspace_doubles(B, 1, 5), nfn_gaussian_mixture_workspace_doubles(B, 1, 5));
+    EXPECT(nfn_posterior_kernel_mixture_workspace_doubles(B, 1, 100), nfn_kernel_mixture_workspace_doubles(B, 1, 100));
+  }
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 15, 0, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 15, -2, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, -150, 15, 4, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 14, 4, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, -15, 4, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, -1, f, 150, 15, 4, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 15, 4, 10, 1, 0, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, big, 1026, 4, 10, 1, 342, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 15, 4, -1, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(nullptr, 1, f, 150, 15, 4, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, nullptr, 150, 15, 4, 10, 1, 5, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 15, 4, 10, 1, 5, f, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 150, 15, 4, 10, 1, 5, nullptr, nullptr, f, dd, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_gaussian_mixture_f32(f, 1, f, 0, 1023, 4, 0, 1, 341, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_OK);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 0, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, -1000, 100, 4, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 99, 4, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, -1, f, 1000, 100, 4, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 4, f, f, 10, 1, 1025, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 32, f, big, 1024, 4, f, f, 10, 32, 1024, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 4, f, f, -1, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_SHAPE);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(nullptr, 1, f, 1000, 100, 4, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, nullptr, 1000, 100, 4, f, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 4, nullptr, f, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 4, f, nullptr, 10, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 4, f, f, 10, 1, 100, nullptr, f, f, nullptr, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 1000, 100, 4, f, f, 10, 1, 100, nullptr, nullptr, f, dd, nullptr, nullptr), NFN_E_NULLPTR);
+  EXPECT(nfn_posterior_lse_kernel_mixture_f32(f, 1, f, 0, 100, 4, f, f, 0, 1, 100, nullptr, nullptr, f, nullptr, nullptr, nullptr), NFN_OK);
   // communicator
   void* comm = nullptr;
   uint8_t uid[NFN_COMM_ID_BYTES];
