@@ -244,6 +244,100 @@ def flow_forward_fldj(flow_type: str, z: np.ndarray, tk: np.ndarray, d: int):
 
 
 # ---------------------------------------------------------------------------
+# Inverses and Jacobians.  The reference defines neither (``PlanarFlow`` / ``RadialFlow``
+# have no ``_inverse``, ``DistributionLayers.py:223-226``): these restate the mathematics
+# of the forward maps above and are the checker of the sampling kernel, deliberately by
+# other means than the kernel's (no Newton step, no starting guess).
+# ---------------------------------------------------------------------------
+
+
+def planar_inverse(z_out, u_hat, w, b):
+    """``z`` with ``planar_forward(z) == z_out``.  Along ``w`` the map is the scalar equation
+    ``c + q tanh(c + b) = w.z_out`` in ``c = w.z`` with ``q = w.u_hat >= -1`` (``_u_circ``), whose
+    left side is non-decreasing and lies within ``|q|`` of ``c``: plain bisection on
+    ``[w.z_out - |q|, w.z_out + |q|]`` until the bracket stops shrinking; then
+    ``z = z_out - u_hat tanh(c + b)``."""
+    dt = z_out.dtype
+    q = np.sum(w * u_hat, axis=-1, keepdims=True, dtype=dt)
+    wzo = np.sum(w * z_out, axis=-1, keepdims=True, dtype=dt)
+    shape = np.broadcast_shapes(q.shape, wzo.shape, b.shape)
+    lo = np.broadcast_to(wzo - np.abs(q), shape).astype(dt)
+    hi = np.broadcast_to(wzo + np.abs(q), shape).astype(dt)
+    half = dt.type(0.5)
+    for _ in range(4096):  # an fp64 bracket halves at most ~2100 times before it stops
+        mid = lo + half * (hi - lo)
+        inside = (mid > lo) & (mid < hi)  # False once the bracket is two neighbours, and for NaN
+        if not inside.any():
+            break
+        g = mid + q * np.tanh(mid + b) - wzo
+        up = inside & (g < 0)
+        dn = inside & ~(g < 0)
+        lo = np.where(up, mid, lo)
+        hi = np.where(dn, mid, hi)
+    c = lo + half * (hi - lo)  # NaN inputs stay NaN
+    return z_out - u_hat * np.tanh(c + b)
+
+
+def radial_inverse(z_out, alpha, beta, gamma):
+    """``z`` with ``radial_forward(z) == z_out``: ``z - gamma`` keeps its direction and its L1
+    length ``r`` solves ``r (1 + alpha beta / (alpha + r)) = r'``, ``r' = |z_out - gamma|_1``, i.e.
+    ``r^2 + (alpha (1 + beta) - r') r - alpha r' = 0``, whose non-negative root is taken in the form
+    without cancellation for either sign of ``A = alpha (1 + beta) - r'``."""
+    dt = z_out.dtype
+    one, two, four = dt.type(1), dt.type(2), dt.type(4)
+    diff = z_out - gamma
+    rp = np.sum(np.abs(diff), axis=-1, keepdims=True, dtype=dt)
+    A = alpha * (one + beta) - rp
+    disc = np.sqrt(A * A + four * alpha * rp)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.where(A > 0, (two * alpha * rp) / (A + disc), (disc - A) / two)
+        s = one + (alpha * beta) / (alpha + r)
+        return gamma + diff / s
+
+
+def flow_inverse(flow_type: str, z_out: np.ndarray, tk: np.ndarray, d: int) -> np.ndarray:
+    """One bijector's inverse: ``flow_forward_fldj(flow_inverse(z_out))[0] == z_out``."""
+    if flow_type == "planar":
+        u_hat, w, b = planar_params(tk, d)
+        return planar_inverse(z_out, u_hat, w, b)
+    if flow_type == "radial":
+        a, be, g = radial_params(tk, d)
+        return radial_inverse(z_out, a, be, g)
+    if flow_type == "affine":
+        sh, sc = affine_params(tk, d)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (z_out - sh) / sc
+    raise AssertionError(f"unknown flow type {flow_type!r}")
+
+
+def flow_jacobian(flow_type: str, z: np.ndarray, tk: np.ndarray, d: int) -> np.ndarray:
+    """``d forward(z) / d z`` of one bijector in closed form, (B, d, d) with rows = outputs.
+    planar ``I + u_hat psi^T`` (``psi = (1 - tanh^2) w``); radial ``(1 + alpha beta h) I +
+    alpha beta h' (z - gamma) sign(z - gamma)^T`` (``h' = -1 / (alpha + r)^2``, L1 ``r``); affine
+    ``diag(scale)``."""
+    dt = z.dtype
+    B = max(z.shape[0], tk.shape[0])
+    eye = np.broadcast_to(np.eye(d, dtype=dt), (B, d, d))
+    if flow_type == "planar":
+        u_hat, w, b = planar_params(tk, d)
+        th = np.tanh(_planar_wzb(z, w, b))
+        psi = (dt.type(1) - th ** 2) * w
+        return eye + np.broadcast_to(u_hat, (B, d))[:, :, None] * np.broadcast_to(psi, (B, d))[:, None, :]
+    if flow_type == "radial":
+        a, be, g = radial_params(tk, d)
+        diff = np.broadcast_to(z - g, (B, d))
+        r = np.sum(np.abs(diff), axis=-1, keepdims=True, dtype=dt)
+        h = dt.type(1) / (a + r)
+        dh = -h * h
+        ab = a * be
+        return (dt.type(1) + ab * h)[:, :, None] * eye + (ab * dh)[:, :, None] * diff[:, :, None] * np.sign(diff)[:, None, :]
+    if flow_type == "affine":
+        _, sc = affine_params(tk, d)
+        return eye * np.broadcast_to(sc, (B, d))[:, None, :]
+    raise AssertionError(f"unknown flow type {flow_type!r}")
+
+
+# ---------------------------------------------------------------------------
 # Base distribution (``DistributionLayers.py:280-294``)
 # ---------------------------------------------------------------------------
 
@@ -321,6 +415,30 @@ def log_pdf(y, t, flow_types, d, trainable_base, y_mean=None, y_std=None, dtype=
     y_circ = normalize_y(y, y_mean, y_std, dt)
     lp = chain_log_prob(y_circ, t, flow_types, d, trainable_base, dt)
     return lp - np.sum(np.log(np.asarray(y_std, dtype=dt)), dtype=dt)
+
+
+def chain_sample(eps, t, flow_types, d, trainable_base, y_mean=None, y_std=None, dtype=np.float64):
+    """The distribution's sampling map for given standard-normal ``eps``:
+    ``y = f_0^-1(... f_{K-1}^-1(loc + scale eps))`` (``eps`` itself over a fixed base), then
+    ``y * y_std + y_mean`` when the estimator normalises y (``BaseEstimator.py:85`` inverted).
+    ``eps``: (B or 1, d); ``t``: (B or 1, P).  Returns ``(y (B, d), log_prob (B,))`` with
+    ``log_prob = log_pdf(y, ...)`` of the returned y; every op rounds to ``dtype``."""
+    dt = np.dtype(dtype)
+    eps = np.asarray(eps, dtype=dt)
+    t = np.asarray(t, dtype=dt)
+    assert eps.shape[-1] == d
+    base_block, blocks = split_params(t, flow_types, d, trainable_base)
+    B = max(eps.shape[0], t.shape[0])
+    loc, scale = base_params(base_block, d, trainable_base, dt)
+    z = eps if loc is None else loc + scale * eps
+    z = np.broadcast_to(z, (B, d)).astype(dt)
+    for ft, tk in zip(reversed(list(flow_types)), reversed(blocks)):
+        z = flow_inverse(ft, z, tk, d)
+    if y_mean is not None:
+        z = z * np.asarray(y_std, dtype=dt) + np.asarray(y_mean, dtype=dt)
+    with np.errstate(all="ignore"):
+        lp = log_pdf(z, t, flow_types, d, trainable_base, y_mean, y_std, dt)
+    return z, lp
 
 
 def posterior_lse(y, t_draws, flow_types, d, trainable_base, y_mean=None, y_std=None, dtype=np.float64):

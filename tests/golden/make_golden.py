@@ -49,7 +49,35 @@ def chain_case(name, flow_types, d, trainable, B, seed, t_scale=1.0, y_bcast=Fal
     return arrs
 
 
+def sample_stress_case():
+    """The sampler's planar regimes (tests/sample_cases.py): inputs and the fp64 oracle's
+    own samples and log-densities.  Everything in it comes from this project's oracle."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import sample_cases as S
+
+    t, eps = S.stress_fixture_inputs()
+    y64, lp64 = O.chain_sample(eps, t, S.FIXTURE_FT, 1, True, dtype=np.float64)
+    np.savez_compressed(os.path.join(HERE, "sample_stress_d1.npz"), t=t, eps=eps, y64=y64, lp64=lp64,
+                        flow_types=np.array(S.FIXTURE_FT, dtype="U8"), d=np.int32(1), trainable=np.int32(1))
+    return "sample_stress_d1"
+
+
+def write_manifest(made, keep=()):
+    with open(os.path.join(HERE, "MANIFEST.txt"), "w") as f:
+        for line in keep:
+            f.write(line)
+        for m in made:
+            h = hashlib.sha256(open(os.path.join(HERE, m + ".npz"), "rb").read()).hexdigest()[:16]
+            f.write(f"{m}.npz {h}\n")
+
+
 def main():
+    if sys.argv[1:] == ["sample_stress_d1"]:  # this fixture alone; the other MANIFEST lines stay
+        name = sample_stress_case()
+        keep = [ln for ln in open(os.path.join(HERE, "MANIFEST.txt")) if not ln.startswith(name + ".npz ")]
+        write_manifest([name], keep)
+        print("wrote", name)
+        return
     made = []
     # C1 plumbing: NFN d=1, ("radial","radial"), B=4096, data from the reference generator.
     sys.path.insert(0, REFERENCE)
@@ -116,10 +144,8 @@ def main():
                                 fwd32=f32, ldj32=l32, sym_t=ones, sym_z=sym, sym_fwd64=sf64, sym_ldj64=sl64,
                                 d=np.int32(d))
             made.append(f"flow_{ftype}_d{d}")
-    with open(os.path.join(HERE, "MANIFEST.txt"), "w") as f:
-        for m in made:
-            h = hashlib.sha256(open(os.path.join(HERE, m + ".npz"), "rb").read()).hexdigest()[:16]
-            f.write(f"{m}.npz {h}\n")
+    made.append(sample_stress_case())
+    write_manifest(made)
     print("wrote", len(made), "fixtures")
 
 

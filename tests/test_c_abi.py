@@ -214,3 +214,45 @@ def test_flow_vjp_entry_point_validates(native_lib):
     assert "NULL" in _lib.last_error()
     assert f(1, fake, 1, fake, 3, 10, 1, None, None, None, None, None) == _lib.NFN_OK         # nothing requested
     assert f(1, fake, 1, fake, 3, 0, 1, None, None, fake, fake, None) == _lib.NFN_OK          # empty batch
+
+
+def test_sample_entry_point_validates(native_lib):
+    """nfn_chain_sample_f32 returns the documented codes and sets nfn_last_error before any
+    HIP call (no pointer below is dereferenced)."""
+    from normalizingflownetwork_amd import _lib
+
+    f = native_lib.nfn_chain_sample_f32
+    fake = 0x1000
+    p_ids = ctypes.cast(_ids("planar", "radial"), ctypes.c_void_p)  # d = 1: P = 3 + 3 + 2 = 8
+
+    def call(eps_bs=1, t_rs=8, B=10, d=1, ids=p_ids, K=2, tr=1, ym=None, ys=None, eps=fake, t=fake, y=fake, lp=fake):
+        return f(eps, eps_bs, t, t_rs, B, d, ids, K, tr, ym, ys, y, lp, None)
+
+    def rejected(code, word, **kw):
+        assert call(**kw) == code, kw
+        assert word in _lib.last_error(), (kw, _lib.last_error())
+
+    rejected(_lib.NFN_E_SHAPE, "n_dims", d=0, t_rs=64)
+    rejected(_lib.NFN_E_SHAPE, "n_dims", d=33, t_rs=4096)
+    many = (ctypes.c_int32 * 65)(*([1] * 65))
+    rejected(_lib.NFN_E_FLOW_ID, "number of flows", ids=ctypes.cast(many, ctypes.c_void_p), K=65, t_rs=4096)
+    bad = (ctypes.c_int32 * 2)(0, 3)
+    rejected(_lib.NFN_E_FLOW_ID, "unknown flow id 3", ids=ctypes.cast(bad, ctypes.c_void_p))
+    rejected(_lib.NFN_E_NULLPTR, "flow_ids", ids=None)
+    rejected(_lib.NFN_E_SHAPE, "batch", B=-1)
+    rejected(_lib.NFN_E_SHAPE, "eps", d=3, eps_bs=2, t_rs=64)   # eps_bstride in (0, d)
+    rejected(_lib.NFN_E_SHAPE, "eps", eps_bs=-1)
+    rejected(_lib.NFN_E_SHAPE, "t row stride", t_rs=7)           # t_rowstride in (0, P)
+    rejected(_lib.NFN_E_SHAPE, "t row stride", t_rs=-8)
+    rejected(_lib.NFN_E_NULLPTR, "y_mean", ym=fake)               # y_mean without y_std
+    rejected(_lib.NFN_E_NULLPTR, "y_mean", ys=fake)
+    rejected(_lib.NFN_E_NULLPTR, "eps", eps=None)
+    rejected(_lib.NFN_E_NULLPTR, "y_out", y=None)
+    rejected(_lib.NFN_E_NULLPTR, "t is NULL", t=None)
+    # an empty batch is a no-op whatever the pointers; broadcast strides (0) are legal
+    assert call(B=0, eps=None, t=None, y=None, lp=None) == _lib.NFN_OK
+    assert call(B=0, eps=None, t=None, y=None, lp=None, eps_bs=0, t_rs=0) == _lib.NFN_OK
+    assert call(B=0, eps=None, t=None, y=None, lp=None, ids=None, K=0, tr=0, t_rs=0) == _lib.NFN_OK
+    assert _lib.last_error() == ""
+    # the bad shape is reported before the empty batch returns
+    assert call(B=0, t_rs=7) == _lib.NFN_E_SHAPE

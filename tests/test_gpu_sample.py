@@ -4,13 +4,23 @@ Size-independent properties: the fp64 oracle's forward chain maps each sample ba
 onto loc + scale * eps (inverse then forward is the identity); the sample's
 log-density equals the forward kernel's log_prob of the sample; and a 2^20-draw
 sample from one fixed parameter row matches the CDF integrated from the density
-(density-grid kernel)."""
+(density-grid kernel).
+
+Per-sample parity (both math modes): every sample's backward error in units of the
+rounding the inverse walk cannot avoid (tests/sample_cases.py ``backward_error``), against
+four times what the oracle's own fp32 sampler reaches on the same inputs; every sample's
+log-density against the oracle's ``log_pdf`` of that sample at the forward kernels' bar;
+over the hard regimes of the iterative inverse (their defining conditions are asserted on
+the CPU, tests/test_sample_oracle.py), every DM instantiation, every tile height, the
+normalised-y store, fixed bases, broadcast and strided rows, and NaN rows."""
 
 import numpy as np
 import pytest
 import torch
 
+import sample_cases as S
 from oracle import nfn_oracle as O
+from parity import check_bound, check_forward, fp32_sensitivity
 
 pytestmark = pytest.mark.gpu
 
@@ -64,16 +74,12 @@ def test_inverse_then_forward_is_identity(ft, d, gpu):
     assert torch.quantile(diff, 0.999) < 1e-4
 
 
-def test_samples_follow_the_density(gpu):
-    """One fixed parameter row of the C2 chain: the empirical CDF of 2^20 samples vs
-    the CDF integrated from the density on a fine grid (KS distance)."""
+def _ks_distance(t1, eps, ft, d):
+    """KS distance of the samples' empirical CDF from the CDF integrated from the density on a
+    fine grid (density-grid kernel), and that integral."""
     from normalizingflownetwork_amd import ops
 
-    ft, d = ("planar", "radial") * 5, 1
-    P = O.total_param_size(ft, d, True)
-    t1 = (0.8 * np.random.default_rng(3).standard_normal((1, P))).astype(np.float32)
-    n = 1 << 20
-    eps = torch.randn((n, 1), generator=torch.Generator(device="cuda").manual_seed(5), device="cuda")
+    n = eps.shape[0]
     y, _ = ops.chain_sample(eps, torch.from_numpy(t1).cuda(), ft, d, True, want_log_prob=False)
     ys = np.sort(y.cpu().numpy().reshape(-1).astype(np.float64))
     lo, hi = ys[0] - 1.0, ys[-1] + 1.0
@@ -81,9 +87,37 @@ def test_samples_follow_the_density(gpu):
     dens = np.exp(ops.chain_log_prob_grid(torch.from_numpy(grid.astype(np.float32)[:, None]).cuda(),
                                           torch.from_numpy(t1).cuda(), ft, d, True).cpu().numpy()[:, 0].astype(np.float64))
     cdf = np.concatenate([[0.0], np.cumsum(0.5 * (dens[1:] + dens[:-1]) * np.diff(grid))])
-    assert abs(cdf[-1] - 1.0) < 2e-3  # the density integrates to one
     ecdf_at = np.searchsorted(ys, grid, side="right") / n
-    ks = np.max(np.abs(ecdf_at - cdf / cdf[-1]))
+    return np.max(np.abs(ecdf_at - cdf / cdf[-1])), cdf[-1]
+
+
+# The second KS case's row: np.random.default_rng(4) at 2.0 * randn has planar q = w.u_hat of
+# (-0.76, -0.65, 0.14, 4.15, -0.31).  On the CPU the fp64 oracle's sampler on the same 2^20 eps
+# is at KS distance 9.4e-4 from the fp64 oracle's density (integral 1 - 4e-9), under the 1.5e-3
+# asked of the seed (seeds 0, 1, 5 gave 7.5e-4, 6.3e-4, 7.4e-4; 2 and 3 have no q > 1).
+KS_SEED = 4
+
+
+def test_samples_follow_the_density(gpu):
+    """One fixed parameter row of the C2 chain: the empirical CDF of 2^20 samples vs
+    the CDF integrated from the density on a fine grid (KS distance).  Second case: a row
+    drawn at 2.0 * randn, some of whose planar flows have q = w.u_hat > 1 (the bisection
+    fallback), with eps drawn on the host so that the fp64 oracle's sampler saw the same draws."""
+    ft, d = ("planar", "radial") * 5, 1
+    P = O.total_param_size(ft, d, True)
+    t1 = (0.8 * np.random.default_rng(3).standard_normal((1, P))).astype(np.float32)
+    n = 1 << 20
+    eps = torch.randn((n, 1), generator=torch.Generator(device="cuda").manual_seed(5), device="cuda")
+    ks, total = _ks_distance(t1, eps, ft, d)
+    assert abs(total - 1.0) < 2e-3  # the density integrates to one
+    assert ks < 3e-3, ks
+    t2 = (2.0 * np.random.default_rng(KS_SEED).standard_normal((1, P))).astype(np.float32)
+    q = [float((w * uh).sum()) for uh, w, _ in (O.planar_params(tk, d) for tk in
+                                                O.split_params(t2.astype(np.float64), ft, d, True)[1][0::2])]
+    assert max(q) > 1.0 and min(q) >= -1.0, q
+    eps2 = np.random.default_rng(KS_SEED + 1000).standard_normal((n, 1)).astype(np.float32)
+    ks, total = _ks_distance(t2, torch.from_numpy(eps2).cuda(), ft, d)
+    assert abs(total - 1.0) < 2e-3
     assert ks < 3e-3, ks
 
 
@@ -99,3 +133,170 @@ def test_distribution_sample_shapes(gpu):
     again, _ = dist.sample_and_log_prob((3,), seed=11)
     assert torch.equal(s, again)
     np.testing.assert_allclose(lp.cpu().numpy(), dist.log_prob(s.reshape(3, 7, 2)).cpu().numpy(), rtol=1e-4, atol=1e-4)
+
+
+# ---- per-sample parity against the fp64 oracle ----------------------------------------------
+
+
+@pytest.fixture(params=["fast", "precise"])
+def math_mode(request, gpu):
+    from normalizingflownetwork_amd import ops
+
+    prev = ops.set_math_mode(request.param)
+    yield request.param
+    ops.set_math_mode(prev)
+
+
+def _cuda(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _sample(case, **kw):
+    from normalizingflownetwork_amd import ops
+
+    y, lp = ops.chain_sample(_cuda(case["eps"]), _cuda(case["t"]), case["ft"], case["d"], case["trainable"],
+                             case["y_mean"], case["y_std"], **kw)
+    return y.cpu().numpy(), None if lp is None else lp.cpu().numpy()
+
+
+def _check_sample(key, case, mode):
+    """One launch: every sample's backward error against 4 max(1, R_ref) units (R_ref: what the
+    oracle's fp32 sampler reaches on this case; the 4 is the gap between the kernel's fast
+    primitives — a tanh within 3.2 ulp, reciprocal-based division — and numpy's correctly
+    rounded ones, the same for the precise mode), and every sample's log-density against the
+    oracle's log_pdf of that very sample, at the forward kernels' bar."""
+    from normalizingflownetwork_amd import ops
+
+    ft, d, tr, ym, ys = case["ft"], case["d"], case["trainable"], case["y_mean"], case["y_std"]
+    what = f"sample {key} [{mode}]"
+    y, lp = _sample(case)
+    B = max(case["eps"].shape[0], case["t"].shape[0])
+    assert y.shape == (B, d) and lp.shape == (B,)
+    assert np.isfinite(y).all() and np.isfinite(lp).all(), what
+    z, target, err, unit = S.backward_error(case, y)
+    r_ref = S.reference_ratio(key, case)
+    print(f"{what}: R_ref {r_ref:.3g}, gpu max err/unit {float((err / unit).max()):.3g}")
+    check_bound(z, target, (4.0 * max(1.0, r_ref) * unit)[:, None], what, kind="sample")
+    with np.errstate(all="ignore"):
+        r64 = O.log_pdf(y, case["t"], ft, d, tr, ym, ys, np.float64)
+        r32 = O.log_pdf(y, case["t"], ft, d, tr, ym, ys, np.float32)
+    sens = fp32_sensitivity(y, case["t"], ft, d, tr, ym, ys)
+    check_forward(lp, r64, r32, what + " log_prob", kind="sample_logp", sensitivity=sens)
+    # and the forward kernel's log_prob of the sample meets the same truth
+    lp_fwd, _ = ops.chain_log_prob(_cuda(y), _cuda(case["t"]), ft, d, tr, ym, ys)
+    check_forward(lp_fwd.cpu().numpy(), r64, r32, what + " forward log_prob", kind="sample_logp", sensitivity=sens)
+    return y, lp
+
+
+@pytest.mark.parametrize("name", sorted(S.REGIME_CASES))
+def test_regimes(math_mode, name):
+    case = S.regime_case(name)
+    y, _ = _check_sample(name, case, math_mode)
+    if name.startswith("radial-"):  # one flow: a target on gamma (r' = 0) returns gamma itself
+        on = case["on_gamma"]
+        np.testing.assert_array_equal(y[on], case["t"][on][:, 2:])
+
+
+@pytest.mark.parametrize("name", sorted(S.SHAPES))
+def test_shapes_and_paths(math_mode, name):
+    ft, d, B, _, kw = S.SHAPES[name]
+    case = S.random_case(ft, d, B, 900 + len(name) + B, **kw)
+    y, lp = _check_sample(name, case, math_mode)
+    if name == "k-no-flows-fixed-base":
+        np.testing.assert_array_equal(y, case["eps"])
+
+
+@pytest.mark.parametrize("ft,d", [(S.C2, 1), (("planar",) * 6, 2)])  # P = 32 (float4 rows) and P = 34
+def test_t_views_and_broadcasts(math_mode, ft, d):
+    """A broadcast t row with log_prob, a broadcast eps row, and t as columns of a wider tensor
+    (misaligned: the scalar staging path; 16-byte aligned: the float4 one) equal the contiguous
+    call bit for bit."""
+    from normalizingflownetwork_amd import ops
+
+    B = 2 * 256 + 3
+    c = S.random_case(ft, d, B, 77 + d)
+    P = c["t"].shape[1]
+    eps, t = _cuda(c["eps"]), _cuda(c["t"])
+    y, lp = ops.chain_sample(eps, t, ft, d, True)
+    # one t row against B rows of eps
+    y1, lp1 = ops.chain_sample(eps, t[:1], ft, d, True)
+    yr, lpr = ops.chain_sample(eps, t[:1].expand(B, P).contiguous(), ft, d, True)
+    assert torch.equal(y1, yr) and torch.equal(lp1, lpr)
+    _check_sample(f"bcast-t d={d}", dict(c, t=c["t"][:1]), math_mode)
+    # one eps row against B rows of t
+    y1, lp1 = ops.chain_sample(eps[:1], t, ft, d, True)
+    yr, lpr = ops.chain_sample(eps[:1].expand(B, d).contiguous(), t, ft, d, True)
+    assert tuple(y1.shape) == (B, d) and torch.equal(y1, yr) and torch.equal(lp1, lpr)
+    # column views
+    for off, pad in ((3, 7), (4, 8)):
+        wide = torch.full((B, P + pad), float("nan"), device="cuda")
+        wide[:, off:off + P] = t
+        view = wide[:, off:off + P]
+        assert (view.data_ptr() % 16 == 0) == (off == 4) and view.stride(0) == P + pad
+        yv, lpv = ops.chain_sample(eps, view, ft, d, True)
+        assert torch.equal(yv, y) and torch.equal(lpv, lp), (off, pad)
+
+
+def test_nonfinite_rows(math_mode):
+    """NaN eps rows and a NaN parameter give non-finite y and log_prob on those rows only (the
+    planar loop leaves through its !(|dx| > tol) exit and the call returns); every other row
+    equals the clean run bit for bit."""
+    c = S.random_case(S.C2, 1, 257, 31)
+    y, lp = _sample(c)
+    bad = dict(c, eps=c["eps"].copy(), t=c["t"].copy())
+    bad["eps"][[0, 64, 256]] = np.nan
+    bad["t"][100, 2 + 3 * 5] = np.nan  # u of the planar flow in the middle of the chain
+    yb, lpb = _sample(bad)
+    rows = np.array([0, 64, 100, 256])
+    assert not np.isfinite(yb[rows]).any() and not np.isfinite(lpb[rows]).any()
+    keep = np.setdiff1d(np.arange(257), rows)
+    np.testing.assert_array_equal(yb[keep], y[keep])
+    np.testing.assert_array_equal(lpb[keep], lp[keep])
+
+
+@pytest.mark.parametrize("ft,d", [(S.C2, 1), (("affine",) + ("planar",) * 4 + ("radial",) * 4, 8)])
+def test_structure(math_mode, ft, d):
+    """The same call twice, a row permutation, and a prefix of the batch: bitwise."""
+    B = 4099
+    c = S.random_case(ft, d, B, 55 + d)
+    y, lp = _sample(c)
+    y2, lp2 = _sample(c)
+    np.testing.assert_array_equal(y, y2)
+    np.testing.assert_array_equal(lp, lp2)
+    perm = np.random.default_rng(1).permutation(B)
+    yp, lpp = _sample(dict(c, eps=c["eps"][perm], t=c["t"][perm]))
+    np.testing.assert_array_equal(yp, y[perm])
+    np.testing.assert_array_equal(lpp, lp[perm])
+    yh, lph = _sample(dict(c, eps=c["eps"][:1000], t=c["t"][:1000]))
+    np.testing.assert_array_equal(yh, y[:1000])
+    np.testing.assert_array_equal(lph, lp[:1000])
+    yn, none = _sample(c, want_log_prob=False)
+    assert none is None
+    np.testing.assert_array_equal(yn, y)
+
+
+@pytest.mark.parametrize("ft,d,batch", [(("planar", "radial", "affine"), 16, (7,)), (S.C2, 1, (2, 5))])
+def test_layer_sample_and_log_prob(math_mode, ft, d, batch):
+    from normalizingflownetwork_amd import InverseNormalizingFlowLayer
+
+    layer = InverseNormalizingFlowLayer(ft, d, True)
+    P = layer.get_total_param_size()
+    t = (0.5 * np.random.default_rng(d).standard_normal(batch + (P,))).astype(np.float32)
+    dist = layer(t)
+    s, lp = dist.sample_and_log_prob((3,), seed=11)
+    assert tuple(s.shape) == (3,) + batch + (d,) and tuple(lp.shape) == (3,) + batch
+    assert tuple(dist.sample((3,), seed=11).shape) == (3,) + batch + (d,)
+    again, lp_again = dist.sample_and_log_prob((3,), seed=11)
+    assert torch.equal(s, again) and torch.equal(lp, lp_again)
+    other, _ = dist.sample_and_log_prob((3,), seed=12)
+    assert not torch.equal(s, other)
+    # rows are ordered (draw, batch): the oracle's log_pdf of each sample under its own row
+    sn = s.cpu().numpy().reshape(-1, d)
+    tn = np.tile(t.reshape(-1, P), (3, 1))
+    r64 = O.log_pdf(sn, tn, ft, d, True, None, None, np.float64)
+    r32 = O.log_pdf(sn, tn, ft, d, True, None, None, np.float32)
+    sens = fp32_sensitivity(sn, tn, ft, d, True)
+    what = f"layer sample d={d} batch={batch} [{math_mode}]"
+    check_forward(lp.cpu().numpy().reshape(-1), r64, r32, what, kind="sample_logp", sensitivity=sens)
+    check_forward(dist.log_prob(s).cpu().numpy().reshape(-1), r64, r32, what + " dist.log_prob", kind="sample_logp",
+                  sensitivity=sens)
