@@ -74,6 +74,13 @@
  *                             (BayesKernelMixtureNetwork)
  *                                                    estimators/BayesKernelMixtureNetwork.py,
  *                                                    estimators/BayesianNNEstimator.py:65-76
+ *   nfn_mean_field_draw_kl_f32 /
+ *   nfn_mean_field_draw_kl_grad_f32
+ *                          <- the weight draw and the KL(q || p) loss of every DenseVariational
+ *                             layer (posterior / prior: MeanFieldLayer), and the gradient TF's
+ *                             tape takes through both when BayesianNNEstimator trains
+ *                                                    estimators/BayesianNNEstimator.py:42-63,78-146,
+ *                                                    estimators/DistributionLayers.py:17-71
  *   nfn_comm_* /
  *   nfn_allreduce_mean     <- the mean of score()/mle_log_likelihood_score over a batch
  *                             sharded across GPUs (one RCCL all-reduce of {sum, count})
@@ -115,7 +122,8 @@ extern "C" {
  *                no version change (additive, every earlier entry unchanged), the four
  *                nfn_kernel_mixture_* entries, the three nfn_gaussian_mixture_* entries,
  *                and nfn_posterior_lse_gaussian_mixture_f32 / nfn_posterior_lse_kernel_mixture_f32
- *                with their two workspace queries.
+ *                with their two workspace queries, and nfn_mean_field_draw_kl_f32 /
+ *                nfn_mean_field_draw_kl_grad_f32 with nfn_mean_field_workspace_doubles.
  *   202 (0.2.2): + nfn_flow_vjp_f32 (additive).
  *   201 (0.2.1): + nfn_split_blocks_f32 (additive; every 200 entry point unchanged).
  *   200 (0.2.0): out_sum is a device double[2] {sum, non-finite count} (was double[1]);
@@ -477,6 +485,44 @@ int32_t nfn_posterior_lse_kernel_mixture_f32(const float* y, int64_t y_bstride, 
                                              const float* locs, const float* scales, int64_t B, int32_t d, int32_t M,
                                              const float* y_mean, const float* y_std, float* out_lse,
                                              double* out_sum, double* workspace, void* stream);
+
+/*
+ * The mean-field posterior of a Bayesian net's weights (every tfp DenseVariational layer of
+ * BayesianNNEstimator, posterior and prior built from MeanFieldLayer), for ONE flat vector of
+ * all N variational weights: layers concatenated, each as kernel (in, out) row-major then bias.
+ * Per element, with m = loc[i], s = 1e-3 + softplus(log(e - 1) + 0.05 * rho[i]),
+ * p = prior_loc[i] (0 when prior_loc is NULL) and sp = prior_scale:
+ *   out_w[i] = m + s * eps[i]                                    (one fma)
+ *   kl_exact != 0 : KL = sum_i log(sp / s) + (s^2 + (m - p)^2) / (2 sp^2) - 1/2
+ *   kl_exact == 0 : KL = sum_i -log s - eps[i]^2 / 2 + log sp + (w - p)^2 / (2 sp^2)
+ *                   (log q(w) - log p(w) at the same draw, w = m + s * eps[i])
+ * Map mode (rho == NULL and eps == NULL): the posterior is Normal(loc, 1) converted by its mean,
+ * so out_w = loc, the exact KL is sum_i log sp + (1 + (m - p)^2) / (2 sp^2) - 1/2 and the
+ * sampled one sum_i log sp + (m - p)^2 / (2 sp^2).
+ *   loc, rho, eps, prior_loc (nullable), out_w (nullable) : N floats each, any 4-byte alignment
+ *   out_kl (nullable) : device double[2] {KL, number of non-finite terms}; fp64 terms summed in a
+ *                fixed order (bitwise deterministic); needs workspace, a device
+ *                double[nfn_mean_field_workspace_doubles(N)] that needs no initialisation
+ * The backward takes the upstream gradients g_w (N floats, NULL = 0) of out_w and g_kl (a DEVICE
+ * float[1], NULL = 0) of the KL sum, and writes, with s' = 0.05 * sigmoid(log(e - 1) + 0.05 rho):
+ *   grad_loc       = g_w + g_kl * A
+ *   grad_rho       = (g_w * eps + g_kl * Bs) * s'        (not written in map mode)
+ *   grad_prior_loc = -g_kl * A                            (nullable)
+ *   exact: A = (m - p) / sp^2, Bs = -1/s + s / sp^2;  sampled: A = (w - p) / sp^2,
+ *   Bs = -1/s + eps * (w - p) / sp^2;  map mode: A = (m - p) / sp^2
+ * NFN_E_SHAPE: N < 0; prior_scale not > 0 or not finite; rho and eps not both NULL or both given;
+ * out_kl without workspace; the forward with neither out_w nor out_kl; the backward with rho
+ * but no grad_rho.  N == 0 succeeds and writes out_kl = {0, 0}.  One launch up to N = 2^26 and
+ * beyond (a grid-stride loop over a capped grid).
+ */
+int64_t nfn_mean_field_workspace_doubles(int64_t N);
+int32_t nfn_mean_field_draw_kl_f32(const float* loc, const float* rho, const float* eps, const float* prior_loc,
+                                   float prior_scale, int64_t N, int32_t kl_exact, float* out_w, double* out_kl,
+                                   double* workspace, void* stream);
+int32_t nfn_mean_field_draw_kl_grad_f32(const float* loc, const float* rho, const float* eps,
+                                        const float* prior_loc, float prior_scale, int64_t N, int32_t kl_exact,
+                                        const float* g_w, const float* g_kl, float* grad_loc, float* grad_rho,
+                                        float* grad_prior_loc, void* stream);
 
 /*
  * Multi-GPU (one process per GPU, batch sharded over ranks).  The communicator

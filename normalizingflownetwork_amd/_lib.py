@@ -116,6 +116,15 @@ SIGNATURES = {
         [_vp, _c_int64, _vp, _c_int64, _c_int64, _c_int32, _vp, _vp, _c_int64, _c_int32, _c_int32, _vp, _vp, _vp,
          _vp, _vp, _vp],
     ),
+    "nfn_mean_field_workspace_doubles": (_c_int64, [_c_int64]),
+    "nfn_mean_field_draw_kl_f32": (
+        _c_int32,
+        [_vp, _vp, _vp, _vp, ctypes.c_float, _c_int64, _c_int32, _vp, _vp, _vp, _vp],
+    ),
+    "nfn_mean_field_draw_kl_grad_f32": (
+        _c_int32,
+        [_vp, _vp, _vp, _vp, ctypes.c_float, _c_int64, _c_int32, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
     "nfn_comm_unique_id": (_c_int32, [_vp]),
     "nfn_comm_init": (_c_int32, [ctypes.POINTER(_vp), _c_int32, _vp, _c_int32]),
     "nfn_comm_destroy": (_c_int32, [_vp]),

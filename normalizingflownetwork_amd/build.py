@@ -53,6 +53,7 @@ UNITS = [
     ("mixture_precise", "nfn_mixture.hip", ["-DNFN_FAST=0"]),
     ("gmm_fast", "nfn_gmm.hip", ["-DNFN_FAST=1"]),
     ("gmm_precise", "nfn_gmm.hip", ["-DNFN_FAST=0"]),
+    ("meanfield", "nfn_meanfield.hip", []),
     ("sample", "nfn_sample.hip", []),
     ("comm", "nfn_comm.hip", []),
 ]

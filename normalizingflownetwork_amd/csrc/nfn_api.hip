@@ -7,12 +7,13 @@
 // summed output (check_sum_workspace, zero_sum, bind_sum) and the small launch rules
 // (vec4_rows, check_tile_fits, lane_group, ablation_knobs) that the entry points share;
 // chain_prologue and dense_prologue, which build the program, run the common checks and
-// fill the common argument fields; run_chain / run_mixture / run_gmm, each the body of two
-// or more entry points; then the extern "C" functions, every other entry being its own
+// fill the common argument fields; run_chain / run_mixture / run_gmm / run_mean_field, each
+// the body of two or more entry points; then the extern "C" functions, every other entry being its own
 // body.  Within an entry the order of the checks is part of the ABI: the program's errors
 // first, then shape errors, then NULL pointers (an empty batch returns between the two in
 // the chain family, after the pointers in the mixtures).
 #include <atomic>
+#include <cmath>
 #include <string>
 
 #include "nfn_launch.h"
@@ -717,6 +718,58 @@ int32_t run_gmm(bool grad, const Draws* draws, const float* y, int64_t y_bstride
   return check_hip(draws ? "gaussian_mixture_posterior_kernel launch" : "gaussian_mixture_kernel launch");
 }
 
+// Mean-field draw and KL (nfn_meanfield.hip).  A workgroup's pass covers 4 * kMaxBlock
+// elements and the grid-stride grid never exceeds kMeanFieldMaxParts workgroups: ONE
+// function sizes the workspace and caps every launch, whatever N.
+constexpr int64_t kMeanFieldMaxParts = 2048;
+int64_t mean_field_parts(int64_t N) {
+  return std::max<int64_t>(1, std::min<int64_t>(kMeanFieldMaxParts, (N + 4 * kMaxBlock - 1) / (4 * kMaxBlock)));
+}
+
+int32_t run_mean_field(bool grad, const float* loc, const float* rho, const float* eps, const float* prior_loc,
+                       float prior_scale, int64_t N, int32_t kl_exact, const float* g_w, const float* g_kl,
+                       float* out_w, double* out_kl, double* workspace, float* grad_loc, float* grad_rho,
+                       float* grad_prior_loc, void* stream) {
+  g_last_error.clear();
+  const HookScope hook_scope;
+  if (int32_t rc = check_batch(N)) return rc;
+  if (!(prior_scale > 0.0f) || !std::isfinite(prior_scale))
+    return fail(NFN_E_SHAPE, "prior_scale must be > 0 and finite");
+  if ((rho == nullptr) != (eps == nullptr))
+    return fail(NFN_E_SHAPE, "rho and eps must both be given or both NULL (map mode)");
+  if (check_sum_workspace(out_kl, workspace) != NFN_OK)
+    return fail(NFN_E_SHAPE, "workspace is NULL but out_kl requested");
+  if (!grad && !out_w && !out_kl) return fail(NFN_E_SHAPE, "neither out_w nor out_kl requested");
+  if (grad && rho && !grad_rho) return fail(NFN_E_SHAPE, "rho given but grad_rho is NULL");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (N == 0) return zero_sum(out_kl, s);
+  if (!loc) return fail(NFN_E_NULLPTR, "loc is NULL");
+  if (int32_t rc = check_grid((N + 4 * kMaxBlock - 1) / (4 * kMaxBlock))) return rc;
+  MeanFieldArgs a;
+  memset(&a, 0, sizeof(a));
+  a.loc = loc;
+  a.rho = rho;
+  a.eps = eps;
+  a.prior_loc = prior_loc;
+  a.log_ps = log((double)prior_scale);
+  a.inv_2var = 0.5 / ((double)prior_scale * (double)prior_scale);
+  a.N = N;
+  a.kl_exact = kl_exact != 0;
+  a.grid_cap = mean_field_parts(N);
+  if (grad) {
+    a.g_w = g_w;
+    a.g_kl = g_kl;
+    a.grad_loc = grad_loc;
+    a.grad_rho = grad_rho;
+    a.grad_prior_loc = grad_prior_loc;
+  } else {
+    a.out_w = out_w;
+    if (out_kl) bind_sum(a, workspace, out_kl);
+  }
+  launch_mean_field(grad, a, s);
+  return check_hip(grad ? "mean_field_draw_kl_grad_kernel launch" : "mean_field_draw_kl_kernel launch");
+}
+
 }  // namespace
 }  // namespace nfn
 
@@ -1038,6 +1091,26 @@ int32_t nfn_posterior_lse_kernel_mixture_f32(const float* y, int64_t y_bstride, 
   const Draws draws = {logits_drawstride, S};
   return run_mixture(false, &draws, y, y_bstride, logits, logits_rowstride, locs, scales, B, d, M, y_mean, y_std,
                      nullptr, out_lse, out_sum, workspace, nullptr, 0, nullptr, nullptr, nullptr, stream);
+}
+
+int64_t nfn_mean_field_workspace_doubles(int64_t N) {
+  if (N <= 0) return 0;
+  return 2 + 2 * mean_field_parts(N);  // [count | ticket | (sum, count) pairs]
+}
+
+int32_t nfn_mean_field_draw_kl_f32(const float* loc, const float* rho, const float* eps, const float* prior_loc,
+                                   float prior_scale, int64_t N, int32_t kl_exact, float* out_w, double* out_kl,
+                                   double* workspace, void* stream) {
+  return run_mean_field(false, loc, rho, eps, prior_loc, prior_scale, N, kl_exact, nullptr, nullptr, out_w, out_kl,
+                        workspace, nullptr, nullptr, nullptr, stream);
+}
+
+int32_t nfn_mean_field_draw_kl_grad_f32(const float* loc, const float* rho, const float* eps,
+                                        const float* prior_loc, float prior_scale, int64_t N, int32_t kl_exact,
+                                        const float* g_w, const float* g_kl, float* grad_loc, float* grad_rho,
+                                        float* grad_prior_loc, void* stream) {
+  return run_mean_field(true, loc, rho, eps, prior_loc, prior_scale, N, kl_exact, g_w, g_kl, nullptr, nullptr,
+                        nullptr, grad_loc, grad_rho, grad_prior_loc, stream);
 }
 
 int32_t nfn_posterior_lse_dense_f32(const float* y, int64_t y_bstride, const float* h, int64_t h_drawstride,

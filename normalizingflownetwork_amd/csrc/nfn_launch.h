@@ -279,6 +279,34 @@ int64_t launch_gmm_precise(bool grad, const GmmArgs& a, hipStream_t s);
 // per-sample logsumexp over draws - log S
 int64_t launch_gmm_posterior_fast(const GmmArgs& a, hipStream_t s);
 int64_t launch_gmm_posterior_precise(const GmmArgs& a, hipStream_t s);
+// nfn_meanfield.hip: the mean-field draw w = loc + s * eps with KL(q || p)
+// (nfn_mean_field_draw_kl_f32) and its backward, over a flat vector of N weights
+struct MeanFieldArgs {
+  const float* loc;        // (N,)
+  const float* rho;        // (N,) or NULL with eps: map mode
+  const float* eps;
+  const float* prior_loc;  // (N,) or NULL = 0
+  const float* g_w;        // backward: upstream gradient of the draw (N,) or NULL = 0
+  const float* g_kl;       // backward: upstream gradient of the KL sum, device float[1], or NULL = 0
+  float* out_w;            // forward: (N,) or NULL
+  float* grad_loc;         // backward: (N,) each, or NULL
+  float* grad_rho;
+  float* grad_prior_loc;
+  double* partials;        // forward: the workspace's (sum, count) pairs, or NULL
+  double* out_sum;
+  double log_ps;           // log prior_scale
+  double inv_2var;         // 1 / (2 prior_scale^2)
+  int64_t N;
+  int64_t nvec;            // set by the launcher: groups of four elements after the head
+  int64_t grid_cap;        // the workspace's partial slots
+  int32_t head;            // set by the launcher: elements before the first group (<= 3)
+  int32_t tail;            // set by the launcher: elements after the last group (<= 3)
+  uint32_t vec;            // set by the launcher: per array, its groups are 16-byte aligned
+  int32_t kl_exact;
+  uint32_t epoch;
+};
+// returns the grid (= number of partials the forward wrote)
+int64_t launch_mean_field(bool grad, const MeanFieldArgs& a, hipStream_t s);
 // nfn_sample.hip
 void launch_sample(bool fast, int dm, const SampleArgs& sa, dim3 grid, dim3 block, size_t lds, hipStream_t s);
 // nfn_grid.hip

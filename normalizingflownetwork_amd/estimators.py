@@ -11,7 +11,8 @@ HIP kernels: the y normalisation ``(y - mu)/sigma``, the whole flow chain, the
 base density, the ``-sum(log sigma)`` correction and (for ``score``) the fp64
 batch sum.  ``fit`` trains on the GPU: torch autograd through the MLP and the
 fused backward kernel through the flow chain; the Bayesian
-estimator's variational training (KL term) is not mirrored.
+estimator's variational training (``fit(variational=True)``: weight draw, KL term and their
+gradients) runs in the two fused mean-field kernels.
 
 ``KernelMixtureNetwork`` (``estimators/KernelMixtureNetwork.py``) shares all of it: ``fit``
 dispatches through the density layer (its trainable tensors, its differentiable train-time
@@ -293,9 +294,8 @@ class BaseEstimator:
             self._build(int(x.shape[1]))
         dev = ops._device()
         self._mlp.to(dev)
-        params = [p.detach().requires_grad_(True) for p in self._mlp.weights + self._mlp.biases]
-        nw = len(self._mlp.weights)
-        self._mlp.weights, self._mlp.biases = params[:nw], params[nw:]
+        params = self._fit_begin(dev)
+        n_eps = self._fit_draw_size()
         lr = getattr(self, "learning_rate", 3e-3)
         dl = self.dist_layer
         # the layer's own trainable tensors (the kernel mixture's bandwidth variable; a flow
@@ -319,57 +319,65 @@ class BaseEstimator:
         gen = torch.Generator(device=dev).manual_seed(int(self.random_seed))
         n = X.shape[0]
         acc = torch.zeros((), dtype=torch.float64, device=dev)
+        acc_pen = torch.zeros((), dtype=torch.float64, device=dev) if n_eps is not None else None
 
-        def step(idx, nx, ny):
-            """One training step on the rows ``idx`` with the noise draws ``nx`` / ``ny``."""
+        def step(idx, nx, ny, eps):
+            """One training step on the rows ``idx`` with the noise draws ``nx`` / ``ny`` and the
+            weight draw ``eps``."""
             xn = (X[idx] - xm) / (xs + 1e-8)
             if nx is not None:
                 xn = xn + self.x_noise_std * nx
             yc = (Y[idx] - ym) / ys
             if ny is not None:
                 yc = yc + self.y_noise_std * ny
+            mlp, penalty = self._fit_network(eps)
             if fused_dense:  # output layer fused into the chain, forward and backward
-                lp = ops.log_prob_dense(yc, self._mlp.hidden(xn), self._mlp.weights[-1], self._mlp.biases[-1],
+                lp = ops.log_prob_dense(yc, mlp.hidden(xn), mlp.weights[-1], mlp.biases[-1],
                                         dl.flow_types, self.n_dims, dl.trainable_base_dist)
             else:
-                t = self._mlp(xn)
+                t = mlp(xn)
                 lp = dl.train_log_prob(yc, t)  # the layer's differentiable fused log_prob
             loss = -lp.mean() + sum_log_ys
+            if penalty is not None:
+                loss = loss + penalty
+                acc_pen.add_(penalty.detach().double() * idx.numel())
             loss.backward()
             opt.step()
             acc.add_(loss.detach().double() * idx.numel())
 
         def draws(rows):
+            """The step's normal draws, in the fixed order the replay refills them."""
             nx = torch.randn((rows, X.shape[1]), generator=gen, device=dev) if self.x_noise_std > 0 else None
             ny = torch.randn((rows, Y.shape[1]), generator=gen, device=dev) if self.y_noise_std > 0 else None
-            return nx, ny
+            eps = torch.randn((n_eps,), generator=gen, device=dev) if n_eps else None
+            return nx, ny, eps
 
-        graph = None  # (graph, static idx, static x noise, static y noise, its pinned workspaces)
+        graph = None  # (graph, static idx, static draws (x noise, y noise, eps), its pinned workspaces)
         warm = 3  # eager steps before the capture (optimizer state, allocator pools)
         steps_done = 0
-        history = {"loss": []}
+        history = {"loss": []} if acc_pen is None else {"loss": [], "nll": [], "kl": []}
         try:
             for _ in range(epochs):
                 perm = torch.randperm(n, generator=gen, device=dev) if shuffle else torch.arange(n, device=dev)
                 acc.zero_()
+                if acc_pen is not None:
+                    acc_pen.zero_()
                 for i in range(0, n, batch_size):
                     idx = perm[i:i + batch_size]
                     full = idx.numel() == batch_size
                     if use_graph and full and graph is not None:
-                        g_, sidx, snx, sny, _ = graph
+                        g_, sidx, static, _ = graph
                         sidx.copy_(idx)
-                        if snx is not None:
-                            snx.normal_(generator=gen)
-                        if sny is not None:
-                            sny.normal_(generator=gen)
+                        for buf in static:
+                            if buf is not None:
+                                buf.normal_(generator=gen)
                         g_.replay()
                         continue
-                    nx, ny = draws(idx.numel())
+                    noise = draws(idx.numel())
                     if use_graph and full and steps_done >= warm:
                         # capture the full-batch step (the capture itself executes nothing:
                         # this batch then runs as the graph's first replay)
                         sidx = idx.clone()
-                        snx, sny = nx, ny
                         opt.zero_grad(set_to_none=True)
                         side = torch.cuda.Stream(device=dev)
                         side.wait_stream(torch.cuda.current_stream(dev))
@@ -377,10 +385,10 @@ class BaseEstimator:
                         mark = ops.graph_pin_mark()
                         with torch.cuda.stream(side):
                             with torch.cuda.graph(g_, stream=side):
-                                step(sidx, snx, sny)
+                                step(sidx, *noise)
                         torch.cuda.current_stream(dev).wait_stream(side)
                         # the workspaces the capture pinned live exactly as long as this graph
-                        graph = (g_, sidx, snx, sny, ops.take_graph_workspaces(side, mark))
+                        graph = (g_, sidx, noise, ops.take_graph_workspaces(side, mark))
                         g_.replay()
                         continue
                     opt.zero_grad(set_to_none=True)
@@ -388,22 +396,48 @@ class BaseEstimator:
                         side = torch.cuda.Stream(device=dev)  # warm-up on a side stream (capture rules)
                         side.wait_stream(torch.cuda.current_stream(dev))
                         with torch.cuda.stream(side):
-                            step(idx, nx, ny)
+                            step(idx, *noise)
                         torch.cuda.current_stream(dev).wait_stream(side)
                     else:
-                        step(idx, nx, ny)
+                        step(idx, *noise)
                     steps_done += 1
                 ep_loss = float(acc.item()) / n
                 history["loss"].append(ep_loss)
+                if acc_pen is not None:  # loss = nll + kl, the weighted KL term as Keras adds it
+                    ep_kl = float(acc_pen.item()) / n
+                    history["kl"].append(ep_kl)
+                    history["nll"].append(ep_loss - ep_kl)
                 if verbose:
                     print(f"epoch {len(history['loss'])}/{epochs} loss {ep_loss:.6f}", flush=True)
                 if not np.isfinite(ep_loss):  # tf.keras.callbacks.TerminateOnNaN
                     break
         finally:
-            self._mlp.weights = [p.detach() for p in self._mlp.weights]
-            self._mlp.biases = [p.detach() for p in self._mlp.biases]
+            self._fit_end()
             dl.finish_training()
         return history
+
+    # --- what a training step trains: the Bayesian estimator's variational fit overrides these
+    def _fit_begin(self, dev) -> list:
+        """The network's trainable tensors (leaves on ``dev``) for the optimizer."""
+        params = [p.detach().requires_grad_(True) for p in self._mlp.weights + self._mlp.biases]
+        nw = len(self._mlp.weights)
+        self._mlp.weights, self._mlp.biases = params[:nw], params[nw:]
+        return params
+
+    def _fit_draw_size(self) -> Optional[int]:
+        """Length of the N(0, 1) weight draw a step takes after its noise draws; None: the step
+        has no weight draw and no penalty term (0: a penalty, but nothing to draw)."""
+        return None
+
+    def _fit_network(self, eps):
+        """``(network, penalty)`` of one step: the x -> t network to run and the term its loss
+        adds to the batch-mean NLL (None: nothing)."""
+        return self._mlp, None
+
+    def _fit_end(self):
+        """Leave the trained values in the estimator."""
+        self._mlp.weights = [p.detach() for p in self._mlp.weights]
+        self._mlp.biases = [p.detach() for p in self._mlp.biases]
 
 
 class NormalizingFlowNetwork(BaseEstimator):
@@ -504,8 +538,11 @@ class BayesianNNEstimator(BaseEstimator):
     forms ``t`` of the S draws with one batched GEMM and evaluates
     ``logsumexp_s(log_pdf) - log S`` per sample in ONE fused kernel per row chunk (the
     layer's ``posterior_lse``) instead of S model re-runs.
-    ``fit`` trains the posterior means by maximum likelihood; the KL(q || p) term and
-    the scales' training are not mirrored (out of scope)."""
+    ``fit`` trains the posterior means by maximum likelihood; ``fit(variational=True)``
+    trains the reference's objective, mean NLL of one weight draw per step plus
+    ``kl_weight_scale * KL(q || p)``, over means, scales and (``trainable_prior``) the prior
+    means, the draw, the KL and their gradients in the two fused mean-field kernels
+    (``nfn_mean_field_draw_kl_f32`` / ``nfn_mean_field_draw_kl_grad_f32``)."""
 
     def __init__(self, dist_layer, kl_weight_scale, kl_use_exact=True, hidden_sizes=(10,), activation="tanh",
                  learning_rate=3e-2, noise_reg=("fixed_rate", 0.0), trainable_prior=False, map_mode=False,
@@ -518,6 +555,8 @@ class BayesianNNEstimator(BaseEstimator):
         self.kl_weight_scale = kl_weight_scale
         self.learning_rate = learning_rate  # BayesianNNEstimator.py:61-63 (Adam(learning_rate))
         self._post_rho = None
+        self._prior_loc = None  # flat prior means of every weight, set by a variational fit (None: zeros)
+        self._vi = None         # the flat variational variables while fit(variational=True) runs
         super().__init__(dist_layer, n_dims_x=n_dims_x, hidden_sizes=hidden_sizes, activation=activation,
                          random_seed=random_seed, noise_reg=noise_reg)
         self._draw_gen = None
@@ -543,6 +582,95 @@ class BayesianNNEstimator(BaseEstimator):
         if self._post_rho is None:
             return None
         return [(mean_field_scale(rw).to(device), mean_field_scale(rb).to(device)) for rw, rb in self._post_rho]
+
+    # --- variational training ------------------------------------------------------------
+    def _layer_sizes(self) -> list:
+        """Per layer ``kernel.numel(), bias.numel()`` in the flat vector's order."""
+        return [n for w, b in zip(self._mlp.weights, self._mlp.biases) for n in (w.numel(), b.numel())]
+
+    @staticmethod
+    def _flatten(pairs, dev) -> torch.Tensor:
+        """Per-layer ``(kernel, bias)`` pairs as ONE flat vector, each layer as kernel (in, out)
+        row-major then bias: the order TFP's ``DenseVariational`` splits its variable."""
+        return torch.cat([t.detach().to(dev).reshape(-1) for pair in pairs for t in pair])
+
+    def _unflatten(self, flat: torch.Tensor):
+        """``(kernels, biases)`` as contiguous views of ``flat`` (one split, so one backward node)."""
+        parts = flat.split(self._layer_sizes())
+        kernels = [p.view(w.shape) for p, w in zip(parts[0::2], self._mlp.weights)]
+        return kernels, list(parts[1::2])
+
+    def _posterior_flat(self, dev):
+        """``(loc, rho | None, prior_loc | None)`` of the current posterior as flat vectors."""
+        self._mlp.to(dev)
+        loc = self._flatten(zip(self._mlp.weights, self._mlp.biases), dev)
+        rho = None if self._post_rho is None else self._flatten(self._post_rho, dev)
+        prior = None if self._prior_loc is None else self._prior_loc.detach().to(dev).clone()
+        return loc, rho, prior
+
+    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, variational=False, **kwargs):
+        """``BaseEstimator.fit``.  By default the posterior means train by maximum likelihood.
+        ``variational=True`` trains the reference's compiled model (``BayesianNNEstimator.py:
+        42-63, 109-146``): per step ONE ``eps ~ N(0, 1)`` for all weights (after the noise draws,
+        from the same generator), the draw ``w = loc + s * eps`` and KL(q || p) in one fused
+        launch (``ops.mean_field_draw_kl_diff``; backward: one more), the layers' ``W``, ``b`` as
+        views of ``w``, and ``loss = mean NLL + kl_weight_scale * KL`` — Keras adds each layer's
+        ``kl_weight * KL`` to the batch-mean loss, and summing the layers first is the same
+        number.  ``kl_use_exact``, ``prior_scale``, ``trainable_prior`` and ``map_mode`` act as
+        in the reference.  One Adam covers ``loc``, ``rho`` (not in map mode), the prior means
+        (``trainable_prior``) and the density layer's own tensors; the step replays from the same
+        HIP graph, ``eps`` refilled in place.  ``history`` then also holds ``"nll"`` and ``"kl"``
+        (the weighted term), ``"loss"`` being their sum."""
+        self._vi = {} if variational else None
+        try:
+            return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)
+        finally:
+            self._vi = None
+
+    def _fit_begin(self, dev) -> list:
+        if self._vi is None:
+            return super()._fit_begin(dev)
+        loc, rho, prior = self._posterior_flat(dev)
+        if prior is None and self.trainable_prior:
+            prior = torch.zeros_like(loc)
+        train = [loc] + ([] if rho is None else [rho]) + ([prior] if self.trainable_prior else [])
+        for p in train:
+            p.requires_grad_(True)
+        self._vi.update(loc=loc, rho=rho, prior=prior)
+        return train
+
+    def _fit_draw_size(self) -> Optional[int]:
+        if self._vi is None:
+            return None
+        return 0 if self._vi["rho"] is None else int(self._vi["loc"].numel())
+
+    def _fit_network(self, eps):
+        if self._vi is None:
+            return super()._fit_network(eps)
+        v = self._vi
+        w, kl = ops.mean_field_draw_kl_diff(v["loc"], v["rho"], eps, v["prior"], self.prior_scale, self.kl_use_exact)
+        net = _MLP.__new__(_MLP)  # this step's network: the drawn weights in the Dense stack's shapes
+        net.activation = self.activation
+        net.weights, net.biases = self._unflatten(w)
+        return net, self.kl_weight_scale * kl
+
+    def _fit_end(self):
+        if not self._vi:  # maximum likelihood, or a variational fit that failed before it began
+            return super()._fit_end()
+        v = self._vi
+        kernels, biases = self._unflatten(v["loc"].detach().clone())
+        self._mlp.weights, self._mlp.biases = kernels, biases
+        if v["rho"] is not None:
+            self._post_rho = list(zip(*self._unflatten(v["rho"].detach().clone())))
+        self._prior_loc = torch.zeros_like(v["loc"]).detach() if v["prior"] is None else v["prior"].detach()
+
+    def kl_divergence(self) -> float:
+        """Exact ``sum KL(q || p)`` of the current posterior over every weight against the prior
+        ``Normal(prior means, prior_scale)``, summed in fp64 by the mean-field kernel."""
+        loc, rho, prior = self._posterior_flat(ops._device())
+        eps = None if rho is None else torch.zeros_like(loc)
+        _, kl = ops.mean_field_draw_kl(loc, rho, eps, prior, self.prior_scale, kl_exact=True, want_w=False)
+        return float(kl[0].item())
 
     def _last_layer_draws(self, x, n_draws: int):
         """Per posterior draw: the last hidden activations and the sampled output layer,
@@ -579,18 +707,39 @@ class BayesianNNEstimator(BaseEstimator):
                     bs.append(b)
         return torch.stack(hs).contiguous(), torch.stack(ws).contiguous(), torch.stack(bs).contiguous()
 
-    def evaluate(self, x, y, batch_size=None, verbose=0, **kwargs) -> float:
+    def evaluate(self, x, y, batch_size=None, verbose=0, include_kl=False, **kwargs) -> float:
         """Keras ``evaluate`` of ``BayesianNNEstimator``'s compiled loss for ONE posterior
         draw (every ``DenseVariational`` re-samples its weights per call,
         ``BayesianNNEstimator.py:122-145``): the mean NLL of (x, y) under ``t`` of a fresh
-        draw.  The KL(q || p) regularisation term the reference adds is not mirrored
-        (SURVEY.md §2), so this is the NLL part of its loss."""
+        draw.  With ``include_kl`` the layers' regularisation losses are added as Keras does:
+        ``kl_weight_scale * KL(q || p)``, in the estimator's ``kl_use_exact`` form and, for the
+        sampled form, at the very draw the NLL is evaluated at.  Both variants consume the draw
+        generator identically."""
         x = np.asarray(x, np.float32) if not isinstance(x, torch.Tensor) else x
         y = np.asarray(y, np.float32) if not isinstance(y, torch.Tensor) else y
+        if include_kl:
+            dev = ops._device()
+            if self._draw_gen is None:  # as _last_layer_draws creates it
+                self._draw_gen = torch.Generator(device=dev).manual_seed(self.random_seed)
+            before = self._draw_gen.get_state()
         with torch.no_grad():
             t = self.params_draws(x, 1)[0]
             nll = self._get_neg_log_likelihood()(y, self.dist_layer(t))
-        return float(nll.double().mean().item())
+        value = float(nll.double().mean().item())
+        if not include_kl:
+            return value
+        if self.kl_use_exact:
+            return value + self.kl_weight_scale * self.kl_divergence()
+        loc, rho, prior = self._posterior_flat(dev)
+        eps = None
+        if rho is not None:  # the draw's eps again: the layers' randn calls, replayed from the state before it
+            after = self._draw_gen.get_state()
+            self._draw_gen.set_state(before)
+            eps = torch.cat([torch.randn(t_.shape, generator=self._draw_gen, device=dev).reshape(-1)
+                             for pair in zip(self._mlp.weights, self._mlp.biases) for t_ in pair])
+            self._draw_gen.set_state(after)
+        _, kl = ops.mean_field_draw_kl(loc, rho, eps, prior, self.prior_scale, kl_exact=False, want_w=False)
+        return value + self.kl_weight_scale * float(kl[0].item())
 
     def params_draws(self, x, n_draws: int) -> torch.Tensor:
         """``t`` for ``n_draws`` posterior weight samples: (S, B, P)."""
@@ -653,8 +802,8 @@ class BayesMixtureDensityNetwork(BayesianNNEstimator):
     """``estimators/BayesMixtureDensityNetwork.py``: the Bayesian net over a
     ``GaussianMixtureLayer``.  ``score`` is the fused posterior kernel
     ``nfn_posterior_lse_gaussian_mixture_f32``.  ``fit`` trains the posterior means by maximum
-    likelihood through the fused mixture backward; the KL(q || p) term and the scales'
-    training are not mirrored (out of scope)."""
+    likelihood through the fused mixture backward; ``fit(variational=True)`` trains the
+    reference's variational objective (``BayesianNNEstimator.fit``)."""
 
     def __init__(self, n_dims, kl_weight_scale, n_centers=5, **kwargs):
         dist_layer = GaussianMixtureLayer(n_centers=n_centers, n_dims=n_dims)
@@ -675,8 +824,9 @@ class BayesKernelMixtureNetwork(BayesianNNEstimator):
     """``estimators/BayesKernelMixtureNetwork.py``: the Bayesian net over a
     ``GaussianKernelsLayer``.  ``score`` is the fused posterior kernel
     ``nfn_posterior_lse_kernel_mixture_f32``.  ``fit`` trains the posterior means (and the
-    layer's bandwidth variable) by maximum likelihood through the fused mixture backward; the
-    KL(q || p) term and the scales' training are not mirrored (out of scope)."""
+    layer's bandwidth variable) by maximum likelihood through the fused mixture backward;
+    ``fit(variational=True)`` trains the reference's variational objective
+    (``BayesianNNEstimator.fit``)."""
 
     def __init__(self, n_dims, kl_weight_scale, n_centers=50, **kwargs):
         dist_layer = GaussianKernelsLayer(n_centers=n_centers, n_dims=n_dims, trainable_scale=True)
@@ -692,11 +842,12 @@ class BayesKernelMixtureNetwork(BayesianNNEstimator):
                                          trainable_prior=trainable_prior, map_mode=map_mode,
                                          prior_scale=prior_scale)
 
-    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, **kwargs):
+    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, variational=False, **kwargs):
         """``BayesKernelMixtureNetwork.py:47-51``: the kernel centres are set from the normalised
-        targets, then the posterior means train as in ``BaseEstimator.fit``."""
+        targets, then the posterior trains as in ``BayesianNNEstimator.fit``."""
         y = np.asarray(y, np.float32)
         y_mean = np.mean(y, axis=0, dtype=np.float32)
         y_std = np.std(y, axis=0, dtype=np.float32)
         self.dist_layer.set_center_points((y - y_mean) / y_std, seed=int(self.random_seed))
-        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)
+        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, variational=variational,
+                           **kwargs)

@@ -1350,3 +1350,98 @@ def posterior_lse_kernel_mixture(y, logits_draws, locs, scales, y_mean=None, y_s
     )
     _lib.check(rc, "nfn_posterior_lse_kernel_mixture_f32")
     return _with_nonfinite(out, osum, want_nonfinite)
+
+
+# ---------------------------------------------------------------------------
+# Variational training: the mean-field draw and KL(q || p) (nfn_meanfield.hip)
+# ---------------------------------------------------------------------------
+
+def _numel(x) -> int:
+    return int(x.numel()) if isinstance(x, torch.Tensor) else int(np.size(x))
+
+
+def _flat(x, device) -> Optional[torch.Tensor]:
+    """A flat fp32 device vector (a contiguous view stays a view), or None."""
+    return None if x is None else as_device_f32(x, device).reshape(-1)
+
+
+def _mean_field_inputs(loc, rho, eps, prior_loc, prior_scale, **more):
+    """``(loc, rho, eps, prior_loc, N, device, more)`` as flat device vectors of one length.
+    ``rho`` and ``eps`` are both None in map mode.  The lengths are checked before anything
+    touches the device."""
+    N = _numel(loc)
+    assert (rho is None) == (eps is None), "rho and eps must both be given or both None (map mode)"
+    for name, v in dict(rho=rho, eps=eps, prior_loc=prior_loc, **more).items():
+        assert v is None or _numel(v) == N, f"{name} must have {N} elements like loc, got {_numel(v)}"
+    assert float(prior_scale) > 0.0 and np.isfinite(float(prior_scale)), "prior_scale must be > 0 and finite"
+    dev = _device()
+    return (_flat(loc, dev), _flat(rho, dev), _flat(eps, dev), _flat(prior_loc, dev), N, dev,
+            {k: _flat(v, dev) for k, v in more.items()})
+
+
+def mean_field_draw_kl(loc, rho, eps, prior_loc=None, prior_scale: float = 1.0, kl_exact: bool = True,
+                       want_w: bool = True, want_kl: bool = True):
+    """One draw ``w = loc + s * eps`` of the mean-field posterior over a flat vector of weights,
+    ``s = 1e-3 + softplus(log(e - 1) + 0.05 rho)`` (``MeanFieldLayer``,
+    ``DistributionLayers.py:17-71``), and KL(q || p) against ``Normal(prior_loc or 0,
+    prior_scale)`` in the same launch: the closed form with ``kl_exact``, else ``log q(w) -
+    log p(w)`` at that draw (``DenseVariational``'s ``kl_use_exact``).  ``rho = eps = None`` is
+    map mode (include/nfn.h).  Returns ``(w | None, kl_pair | None)``; ``kl_pair`` is the
+    kernel's (2,) fp64 {KL, number of non-finite terms}."""
+    loc, rho, eps, prior_loc, N, dev, _ = _mean_field_inputs(loc, rho, eps, prior_loc, prior_scale)
+    assert want_w or want_kl, "neither w nor kl requested"
+    lib = _lib.load()
+    w, kl, ws = _sum_outputs(N, want_w, want_kl, lambda: lib.nfn_mean_field_workspace_doubles(N), dev)
+    rc = lib.nfn_mean_field_draw_kl_f32(_ptr(loc), _ptr(rho), _ptr(eps), _ptr(prior_loc), float(prior_scale), N,
+                                        int(bool(kl_exact)), _ptr(w), _ptr(kl), _ptr(ws), _stream())
+    _lib.check(rc, "nfn_mean_field_draw_kl_f32")
+    return w, kl
+
+
+def mean_field_draw_kl_grad(loc, rho, eps, prior_loc=None, prior_scale: float = 1.0, kl_exact: bool = True,
+                            g_w=None, g_kl=None, want_grad_prior: bool = False):
+    """Backward of :func:`mean_field_draw_kl` for the upstream gradients ``g_w`` (of the draw,
+    None = 0) and ``g_kl`` (of the KL sum: a one-element device tensor or a number, None = 0):
+    ``(grad_loc, grad_rho | None in map mode, grad_prior_loc | None)``, one launch, no
+    reduction."""
+    loc, rho, eps, prior_loc, N, dev, more = _mean_field_inputs(loc, rho, eps, prior_loc, prior_scale, g_w=g_w)
+    if g_kl is not None:
+        g_kl = as_device_f32(g_kl, dev).reshape(-1)
+        assert g_kl.numel() == 1, "g_kl must have one element"
+    g_loc = torch.empty((N,), dtype=torch.float32, device=dev)
+    g_rho = torch.empty((N,), dtype=torch.float32, device=dev) if rho is not None else None
+    g_prior = torch.empty((N,), dtype=torch.float32, device=dev) if want_grad_prior else None
+    rc = _lib.load().nfn_mean_field_draw_kl_grad_f32(
+        _ptr(loc), _ptr(rho), _ptr(eps), _ptr(prior_loc), float(prior_scale), N, int(bool(kl_exact)),
+        _ptr(more["g_w"]), _ptr(g_kl), _ptr(g_loc), _ptr(g_rho), _ptr(g_prior), _stream())
+    _lib.check(rc, "nfn_mean_field_draw_kl_grad_f32")
+    return g_loc, g_rho, g_prior
+
+
+class _MeanFieldDrawKL(torch.autograd.Function):
+    """The draw and its KL as a differentiable op: forward and backward are the two fused
+    kernels (nothing but the inputs is saved)."""
+
+    @staticmethod
+    def forward(ctx, loc, rho, eps, prior_loc, prior_scale, kl_exact):
+        w, kl = mean_field_draw_kl(loc, rho, eps, prior_loc, prior_scale, kl_exact)
+        ctx.save_for_backward(loc, rho, eps, prior_loc)
+        ctx.meta = (prior_scale, kl_exact)
+        return w, kl[0].float()
+
+    @staticmethod
+    def backward(ctx, g_w, g_kl):
+        loc, rho, eps, prior_loc = ctx.saved_tensors
+        prior_scale, kl_exact = ctx.meta
+        need_prior = prior_loc is not None and ctx.needs_input_grad[3]
+        g_loc, g_rho, g_prior = mean_field_draw_kl_grad(loc, rho, eps, prior_loc, prior_scale, kl_exact, g_w=g_w,
+                                                        g_kl=g_kl, want_grad_prior=need_prior)
+        return g_loc, g_rho, None, g_prior, None, None
+
+
+def mean_field_draw_kl_diff(loc, rho, eps, prior_loc=None, prior_scale: float = 1.0, kl_exact: bool = True):
+    """Differentiable :func:`mean_field_draw_kl`: ``(w (N,), kl)`` with ``kl`` a device fp32
+    scalar; the gradients w.r.t. ``loc``, ``rho`` and ``prior_loc`` come from the fused backward
+    kernel (``eps`` is a constant of the draw)."""
+    loc, rho, eps, prior_loc, _, _, _ = _mean_field_inputs(loc, rho, eps, prior_loc, prior_scale)
+    return _MeanFieldDrawKL.apply(loc, rho, eps, prior_loc, float(prior_scale), bool(kl_exact))

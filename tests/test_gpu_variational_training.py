@@ -1,0 +1,241 @@
+"""``BayesianNNEstimator.fit(variational=True)`` on the GPU: the step's gradients against fp64
+autograd of the same loss (tests/mean_field_oracle.py for the draw and the KL, the existing
+oracles for the density layers), the replayed HIP graph against the eager loop, what the
+training learns, and the estimator's bookkeeping around it."""
+
+import numpy as np
+import pytest
+import torch
+
+from normalizingflownetwork_amd import (BayesKernelMixtureNetwork, BayesMixtureDensityNetwork,
+                                        BayesNormalizingFlowNetwork, ops)
+from normalizingflownetwork_amd.distribution_layers import InverseNormalizingFlowLayer
+from oracle import nfn_grad_oracle as G
+
+import mdn_oracle as MD
+import mean_field_oracle as MF
+import mixture_oracle as MO
+
+pytestmark = pytest.mark.gpu
+
+C = MF.LOG_EXPM1_ONE
+
+
+# --- fp64 torch restatements of the two mixture layers' log_prob (pinned on the numpy oracles below)
+def _mdn_log_prob(y, t, K, d):
+    comp = t[:, :2 * K * d].reshape(-1, K, 2, d)
+    loc, sg = comp[:, :, 0], torch.nn.functional.softplus(0.05 * comp[:, :, 1] + C)
+    ck = (-0.5 * ((y[:, None, :] - loc) / sg) ** 2 - torch.log(sg)).sum(-1) - 0.5 * d * np.log(2 * np.pi)
+    lg = t[:, 2 * K * d:]
+    return torch.logsumexp(lg + ck, -1) - torch.logsumexp(lg, -1)
+
+
+def _kernel_log_prob(y, t, locs, scales, d):
+    z2 = (((y[:, None, :] - locs[None]) / scales[None, :, None]) ** 2).sum(-1)
+    c = -0.5 * z2 - d * torch.log(scales.abs())[None, :] - 0.5 * d * np.log(2 * np.pi)
+    return torch.logsumexp(t + c, -1) - torch.logsumexp(t, -1)
+
+
+def _models(**kw):
+    common = dict(hidden_sizes=(4,), n_dims_x=1, kl_weight_scale=1.0 / 8, trainable_prior=True, prior_scale=0.5, **kw)
+    return {
+        "flow": BayesNormalizingFlowNetwork(1, flow_types=("radial",) * 2, **common),
+        "mdn": BayesMixtureDensityNetwork(1, n_centers=3, **common),
+        "kmn": BayesKernelMixtureNetwork(1, n_centers=3, **common),
+    }
+
+
+@pytest.mark.parametrize("kl_exact,map_mode", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("kind", ["flow", "mdn", "kmn"])
+def test_one_step_gradients_match_fp64_autograd(gpu, kind, kl_exact, map_mode):
+    """d(mean NLL + kl_weight KL) / d(loc, rho, prior_loc) of one step (B = 8, hidden (4,), d = 1)
+    against fp64 autograd, at the tolerances of test_gpu_training.py::
+    test_weight_gradients_match_autodiff_oracle."""
+    m = _models(kl_use_exact=kl_exact, map_mode=map_mode)[kind]
+    dl, d, B = m.dist_layer, 1, 8
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((B, 1)).astype(np.float32)
+    y = (np.cos(x) + 0.3 * rng.standard_normal((B, 1))).astype(np.float32)
+    if kind == "kmn":
+        dl.set_center_points(y, seed=22)
+    # a posterior away from its initial point: scales from about 0.3 to 3, means of order 1
+    m._mlp.weights = [w + 0.5 * torch.from_numpy(rng.standard_normal(tuple(w.shape)).astype(np.float32))
+                      for w in m._mlp.weights]
+    if not map_mode:
+        m._post_rho = [(20 * torch.from_numpy(rng.standard_normal(tuple(rw.shape)).astype(np.float32)),
+                        20 * torch.from_numpy(rng.standard_normal(tuple(rb.shape)).astype(np.float32)))
+                       for rw, rb in m._post_rho]
+    m._mlp.to(gpu)
+    N = sum(m._layer_sizes())
+    m._prior_loc = torch.from_numpy((0.3 * rng.standard_normal(N)).astype(np.float32))
+    eps = None if map_mode else torch.from_numpy(rng.standard_normal(N).astype(np.float32)).to(gpu)
+    # the step as fit runs it
+    m._vi = {}
+    train = m._fit_begin(gpu)
+    layer_params = dl.trainable_parameters(gpu)
+    net, penalty = m._fit_network(eps)
+    xd, yd = torch.from_numpy(x).to(gpu), torch.from_numpy(y).to(gpu)
+    if isinstance(dl, InverseNormalizingFlowLayer) and ops.dense_fusable(4, dl.get_total_param_size(), d):
+        lp = ops.log_prob_dense(yd, net.hidden(xd), net.weights[-1], net.biases[-1], dl.flow_types, d,
+                                dl.trainable_base_dist)
+    else:
+        assert kind != "flow"  # hidden (4,) takes the fused Dense path
+        lp = dl.train_log_prob(yd, net(xd))
+    (-lp.mean() + penalty).backward()
+    got = [p.grad.double().cpu() for p in train]
+    loc, rho, prior = (None if v is None else v.detach().cpu().numpy() for v in (m._vi["loc"], m._vi["rho"],
+                                                                               m._vi["prior"]))
+    m._vi = None
+    dl.finish_training()
+    # fp64 autograd of the same loss
+    f = lambda a: None if a is None else torch.from_numpy(np.asarray(a, np.float64)).requires_grad_(True)
+    loc64, rho64, prior64 = f(loc), f(rho), f(prior)
+    eps64 = None if eps is None else eps.double().cpu()
+    w, terms = MF.draw_kl_terms(loc64, rho64, eps64, prior64, m.prior_scale, kl_exact)
+    sizes = m._layer_sizes()
+    W1, b1, W2, b2 = w.split(sizes)
+    P = dl.get_total_param_size()
+    t = torch.tanh(torch.from_numpy(x).double() @ W1.view(1, 4) + b1) @ W2.view(4, P) + b2
+    y64 = torch.from_numpy(y).double()
+    if kind == "flow":
+        lp64 = G.chain_log_prob_torch(y64, t, dl.flow_types, d, True)
+    elif kind == "mdn":
+        lp64 = _mdn_log_prob(y64, t, 3, d)
+        np.testing.assert_allclose(lp64.detach().numpy(), MD.log_prob(y, t.detach().numpy(), 3, d), rtol=1e-12)
+    else:
+        scales = dl.scales(torch.device("cpu")).detach().double()
+        locs = torch.from_numpy(np.asarray(dl.locs, np.float64))
+        lp64 = _kernel_log_prob(y64, t, locs, scales, d)
+        np.testing.assert_allclose(lp64.detach().numpy(),
+                                   MO.log_prob(y, t.detach().numpy(), dl.locs, scales.numpy()), rtol=1e-12)
+    (-lp64.mean() + m.kl_weight_scale * terms.sum()).backward()
+    kl64 = float(terms.detach().sum())
+    assert abs(float(penalty.detach()) - m.kl_weight_scale * kl64) <= 1e-5 * max(1.0, abs(kl64))
+    ref = [loc64.grad] + ([] if map_mode else [rho64.grad]) + [prior64.grad]
+    assert len(got) == len(ref)
+    for name, g, r in zip(["loc"] + ([] if map_mode else ["rho"]) + ["prior_loc"], got, ref):
+        print(f"{kind} d{name}: max |err| = {float((g - r).abs().max()):.3e}, max |ref| = {float(r.abs().max()):.3e}")
+        torch.testing.assert_close(g, r, rtol=2e-4, atol=2e-5)
+
+
+def _cos_data(n, seed=22):
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-3, 3, (n, 1)).astype(np.float32)
+    y = (np.cos(x) + 0.3 * rng.standard_normal((n, 1))).astype(np.float32)
+    return x, y
+
+
+def _posterior(m):
+    out = [t.detach().cpu().numpy() for t in m._mlp.weights + m._mlp.biases]
+    if m._post_rho is not None:
+        out += [t.detach().cpu().numpy() for pair in m._post_rho for t in pair]
+    return out
+
+
+@pytest.mark.parametrize("noise", [False, True])
+def test_variational_fit_graph_replay_matches_eager(gpu, noise):
+    """The replayed step (``eps`` refilled in place) trains exactly as the eager loop: per-epoch
+    losses and the final ``loc`` and ``rho`` are bitwise equal (the comparison of
+    test_gpu_training.py::test_fit_graph_replay_matches_eager)."""
+    x, y = _cos_data(203, seed=5)  # 6 full batches of 32 + a partial one per epoch
+    out = {}
+    for use_graph in (True, False):
+        m = BayesNormalizingFlowNetwork(1, kl_weight_scale=1.0 / 203, n_flows=2, hidden_sizes=(10,),
+                                        noise_reg=("fixed_rate", 0.1 if noise else 0.0))
+        hist = m.fit(x, y, epochs=4, verbose=0, use_graph=use_graph, variational=True)
+        out[use_graph] = (hist, _posterior(m))
+    assert out[True][0] == out[False][0]
+    assert len(out[True][1]) == 8
+    for a, b in zip(out[True][1], out[False][1]):
+        np.testing.assert_array_equal(a, b)
+
+
+def test_variational_fit_learns_the_scales(gpu):
+    """256 points of y = cos x + 0.3 N(0, 1), hidden (10,), n_flows = 0, lr 0.1, batch 32, 200
+    epochs (1600 replayed steps), kl_weight_scale = 1 / 256.  Mean-only training leaves the
+    posterior scales at their initial 1.0, so the 50-draw score perturbs every weight with unit
+    noise; the variational objective shrinks them.
+
+    Bounds: mean scale < 0.85 (midway between the untrained 1.0 and the worst 0.70 reached) and
+    score gap > 0.2 (half the smallest gap, 0.41, of the issue's CPU figures).  A pure-torch fp32
+    restatement on the CPU generator, re-run over three seeds before the bounds were kept
+    (mean scale, score; mean-only | variational):
+        seed 22: 1.001, -1.721 | 0.647, -1.199   (gap 0.523)
+        seed 23: 1.001, -2.038 | 0.672, -1.185   (gap 0.853)
+        seed 24: 1.001, -1.867 | 0.701, -1.288   (gap 0.578)"""
+    x, y = _cos_data(256)
+    scores, scales = {}, {}
+    for variational in (False, True):
+        m = BayesNormalizingFlowNetwork(1, kl_weight_scale=1.0 / 256, n_flows=0, hidden_sizes=(10,), learning_rate=0.1)
+        m.fit(x, y, epochs=200, batch_size=32, verbose=0, variational=variational)
+        scales[variational] = (sum(float(s.double().sum()) for pair in m.posterior_scales(gpu) for s in pair)
+                               / sum(m._layer_sizes()))
+        scores[variational] = m.score(x, y)
+    print(f"mean posterior scale: mean-only {scales[False]:.3f}, variational {scales[True]:.3f}; "
+          f"score: mean-only {scores[False]:.3f}, variational {scores[True]:.3f}")
+    assert scales[False] == pytest.approx(1.001, abs=2e-3)  # what the default fit leaves
+    assert scales[True] < 0.85
+    assert scores[True] - scores[False] > 0.2
+
+
+def test_history_and_kl_bookkeeping(gpu):
+    x, y = _cos_data(100, seed=7)
+    klw = 1.0 / 100
+    m = BayesNormalizingFlowNetwork(1, kl_weight_scale=klw, n_flows=1, hidden_sizes=(6,), prior_scale=0.7)
+    hist = m.fit(x, y, epochs=3, verbose=0, variational=True)
+    assert set(hist) == {"loss", "nll", "kl"} and all(len(v) == 3 for v in hist.values())
+    for loss, nll, kl in zip(hist["loss"], hist["nll"], hist["kl"]):
+        assert np.isfinite(loss) and kl > 0.0
+        assert loss == pytest.approx(nll + kl, rel=1e-12, abs=1e-12)
+    assert set(m.fit(x, y, epochs=1, verbose=0)) == {"loss"}  # the default fit's history is unchanged
+    # kl_divergence(): the oracle's exact KL of the written-back posterior
+    loc, rho, prior = (v.cpu().numpy() for v in m._posterior_flat(gpu))
+    assert not prior.any()  # trainable_prior=False
+    want = MF.draw_kl(loc, rho, np.zeros_like(loc), None, 0.7, True)[1]
+    assert m.kl_divergence() == pytest.approx(want, rel=1e-5)
+    # evaluate(include_kl=True) adds kl_weight_scale * KL to the same draw's NLL
+    m._draw_gen = None
+    plain = m.evaluate(x, y)
+    m._draw_gen = None
+    assert m.evaluate(x, y, include_kl=True) - plain == pytest.approx(klw * want, rel=1e-5, abs=1e-9)
+    # the sampled form, at the draw the NLL is evaluated at
+    m.kl_use_exact = False
+    gen = torch.Generator(device=gpu).manual_seed(m.random_seed)
+    eps = torch.cat([torch.randn(t.shape, generator=gen, device=gpu).reshape(-1)
+                     for pair in zip(m._mlp.weights, m._mlp.biases) for t in pair]).cpu().numpy()
+    sampled = MF.draw_kl(loc, rho, eps, None, 0.7, False)[1]
+    m._draw_gen = None
+    assert m.evaluate(x, y, include_kl=True) - plain == pytest.approx(klw * sampled, rel=1e-5, abs=1e-7)
+    m._draw_gen = None
+    assert m.evaluate(x, y) == plain
+
+
+def test_map_mode_and_trainable_prior(gpu):
+    x, y = _cos_data(64, seed=9)
+    m = BayesNormalizingFlowNetwork(1, kl_weight_scale=1.0 / 64, n_flows=1, hidden_sizes=(6,), map_mode=True)
+    hist = m.fit(x, y, epochs=2, verbose=0, variational=True)
+    assert m._post_rho is None and m.posterior_scales() is None
+    assert np.isfinite(hist["loss"]).all() and np.isfinite(m.score(x, y))
+    fixed = BayesNormalizingFlowNetwork(1, kl_weight_scale=1.0 / 64, n_flows=1, hidden_sizes=(6,))
+    fixed.fit(x, y, epochs=2, verbose=0, variational=True)
+    assert fixed._prior_loc.numel() == sum(fixed._layer_sizes()) and not fixed._prior_loc.any()
+    moved = BayesNormalizingFlowNetwork(1, kl_weight_scale=1.0 / 64, n_flows=1, hidden_sizes=(6,),
+                                        trainable_prior=True)
+    moved.fit(x, y, epochs=2, verbose=0, variational=True)
+    assert moved._prior_loc.abs().max() > 0 and not moved._prior_loc.requires_grad
+
+
+@pytest.mark.parametrize("cls", [BayesKernelMixtureNetwork, BayesMixtureDensityNetwork])
+def test_mixture_estimators_train_variationally(gpu, cls):
+    """One epoch of ``fit(variational=True)``: finite losses and the output dimensions
+    test_gpu_training.py::test_bayes_model_output_dims checks."""
+    d = 1
+    x = np.linspace([[-1]] * d, [[1]] * d, 10, dtype=np.float32).reshape((10, d))
+    m = cls(d, kl_weight_scale=1.0 / x.shape[0], n_centers=4, hidden_sizes=(16, 16))
+    hist = m.fit(x, x, epochs=1, verbose=0, variational=True)
+    assert all(np.isfinite(v).all() for v in hist.values())
+    out = m(x)
+    assert out.event_shape == [d] and out.batch_shape == [10]
+    assert tuple(out.log_prob([[0.0] * d]).shape) == (10,)
+    assert tuple(m.pdf(x, x).shape) == (10,)
+    assert np.isfinite(m.score(x, x))
