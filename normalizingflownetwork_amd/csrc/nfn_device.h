@@ -458,6 +458,17 @@ __device__ __forceinline__ float base_log_prob(const float (&x)[DM], PTR p, int 
   return -0.5f * sq - (kHalfLog2Pi * (float)d + logdet);
 }
 
+// sum_j log y_std_j, which the caller subtracts from log_prob (BaseEstimator.py:85); 0 without
+// y normalisation.
+template <bool FAST>
+__device__ __forceinline__ float log_std_sum(const float* y_mean, const float* y_std, int d) {
+  float corr = 0.0f;
+  if (y_mean) {
+    for (int j = 0; j < d; ++j) corr += f_log<FAST>(y_std[j]);
+  }
+  return corr;
+}
+
 // z_0 = y (or (y - mean)/std, BaseEstimator.py:85); returns -sum(log std) or 0.
 template <int DM, bool FAST>
 __device__ __forceinline__ float load_y(float (&z)[DM], const ChainArgs& a, int64_t b) {

@@ -139,17 +139,27 @@ __device__ __forceinline__ double gmm_z(float y, float loc, float sg) {
   return ((double)y - (double)loc) * r;
 }
 
-// log-density of component k at the lane's (normalised) y: c_k.
-template <bool FAST>
-__device__ __forceinline__ double gmm_component(const float* p, const float* ys, int d) {
+// log-density of component k (parameters at p: loc (d), raw (d)) at the lane's (normalised)
+// y: c_k.  STASH (the backward's second pass) also overwrites the component's slots with the
+// factors of its gradients, z / sigma over loc_j and (z^2 - 1) / sigma * 0.05 sigmoid(x) over
+// raw_j.
+template <bool FAST, bool STASH>
+__device__ __forceinline__ double gmm_component(std::conditional_t<STASH, float*, const float*> p, const float* ys,
+                                                int d) {
   double q = 0.0;
   float ls = 0.0f;
   for (int j = 0; j < d; ++j) {
     float x;
     const float sg = gmm_sigma(p[d + j], x);
-    const double z = gmm_z(ys[j], p[j], sg);
-    q = fma(z, z, q);
+    const double zd = gmm_z(ys[j], p[j], sg);
+    q = fma(zd, zd, q);
     ls += f_log<FAST>(sg);
+    if constexpr (STASH) {
+      const float z = (float)zd;
+      const float sig = f_div<FAST>(1.0f, 1.0f + f_exp<FAST>(-x));
+      p[j] = f_div<FAST>(z, sg);
+      p[d + j] = fmaf(z, z, -1.0f) * f_div<FAST>(0.05f * sig, sg);
+    }
   }
   return fma(-0.5, q, -(double)(ls + (float)d * kHalfLog2Pi));
 }
@@ -181,12 +191,30 @@ __device__ __forceinline__ float gmm_row(const float* row, const float* ys, int 
   M = -(double)INFINITY;
   acc = 0.0f;
   for (int k = 0; k < K; ++k) {
-    const double c = gmm_component<FAST>(row + 2 * k * d, ys, d);
+    const double c = gmm_component<FAST, false>(row + 2 * k * d, ys, d);
     const float u = gmm_shift(lg[k], ml);
     s0 += f_exp<FAST>(u);
     gmm_push<FAST>(M, acc, (double)u + c);
   }
   return (float)(M + (double)f_log<FAST>(acc)) - f_log<FAST>(s0);
+}
+
+// Stage nr rows of t from src into the wave's LDS rows, in 16-byte pieces where the launcher
+// found that the rows allow it.
+__device__ __forceinline__ void gmm_stage_t(float* tl, const GmmArgs& a, const float* src, int nr, const WaveWalk& wt,
+                                            int lane) {
+  if (a.vec4)
+    wave_stage<true>(tl, src, a.rs, nr, a.S, wt, lane);
+  else
+    wave_stage<false>(tl, src, a.rs, nr, a.S, wt, lane);
+}
+
+// the lane's staged y, normalised in place
+template <bool FAST>
+__device__ __forceinline__ void gmm_normalise_y(float* ys, const GmmArgs& a) {
+  if (a.y_mean) {
+    for (int j = 0; j < a.d; ++j) ys[j] = f_div_acc<FAST>(ys[j] - a.y_mean[j], a.y_std[j]);
+  }
 }
 
 template <bool FAST, bool GRAD>
@@ -201,20 +229,14 @@ __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_kernel(GmmArgs a) 
   float* ys = yl + lane * Sy;
   const WaveWalk wt = make_walk(a.vec4 ? P >> 2 : P, lane);
   const WaveWalk wy = make_walk(d, lane);
-  float corr = 0.0f;
-  if (a.y_mean) {
-    for (int j = 0; j < d; ++j) corr += f_log<FAST>(a.y_std[j]);
-  }
+  const float corr = log_std_sum<FAST>(a.y_mean, a.y_std, d);
   double acc_sum = 0.0;
   int nfc = 0;
   for (int64_t tile = (int64_t)blockIdx.x * nw + wid; tile < a.ntiles; tile += (int64_t)gridDim.x * nw) {
     const int64_t b0 = tile * R;
     const int nr = (int)min((int64_t)R, a.B - b0);
     const float* src = a.t + b0 * a.rs;
-    if (a.vec4)
-      wave_stage<true>(tl, src, a.rs, nr, S, wt, lane);
-    else
-      wave_stage<false>(tl, src, a.rs, nr, S, wt, lane);
+    gmm_stage_t(tl, a, src, nr, wt, lane);
     wave_stage<false>(yl, a.y + b0 * a.y_bstride, a.y_bstride, nr, Sy, wy, lane);
     [[maybe_unused]] float g = 0.0f;
     if constexpr (GRAD) {
@@ -223,9 +245,7 @@ __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_kernel(GmmArgs a) 
     wave_lds_sync();
     if (lane < nr) {
       const int64_t b = b0 + lane;
-      if (a.y_mean) {
-        for (int j = 0; j < d; ++j) ys[j] = f_div_acc<FAST>(ys[j] - a.y_mean[j], a.y_std[j]);
-      }
+      gmm_normalise_y<FAST>(ys, a);
       float ml, s0, acc;
       double M;
       const float lp = gmm_row<FAST>(row, ys, K, d, ml, s0, M, acc) - corr;
@@ -239,20 +259,7 @@ __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_kernel(GmmArgs a) 
         float* lg = row + 2 * K * d;
         for (int k = 0; k < K; ++k) {
           float* p = row + 2 * k * d;
-          double q = 0.0;
-          float ls = 0.0f;
-          for (int j = 0; j < d; ++j) {
-            float x;
-            const float sg = gmm_sigma(p[d + j], x);
-            const double zd = gmm_z(ys[j], p[j], sg);
-            q = fma(zd, zd, q);
-            ls += f_log<FAST>(sg);
-            const float z = (float)zd;
-            const float sig = f_div<FAST>(1.0f, 1.0f + f_exp<FAST>(-x));
-            p[j] = f_div<FAST>(z, sg);                                        // z / sigma
-            p[d + j] = fmaf(z, z, -1.0f) * f_div<FAST>(0.05f * sig, sg);      // (z^2 - 1) / sigma * 0.05 sigmoid(x)
-          }
-          const double c = fma(-0.5, q, -(double)(ls + (float)d * kHalfLog2Pi));
+          const double c = gmm_component<FAST, true>(p, ys, d);  // leaves its factors in p
           const float u = gmm_shift(lg[k], ml);
           const double av = (double)u + c;
           // a removed component (and one whose weight underflows) gets exact zeros through
@@ -294,6 +301,10 @@ __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_kernel(GmmArgs a) 
 // gaussian_mixture_kernel: a tile's y is staged and normalised once, then draw after draw
 // the tile's rows are staged and every lane pushes its gmm_row into its own running (m, acc)
 // (lse_push / lse_finish, nfn_device.h).  One float per sample leaves the kernel.
+// The row's formula is gmm_row's and the staging is gmm_stage_t / gmm_normalise_y.  The opening
+// lines (wave pointers, walks, corr) are written as in gaussian_mixture_kernel, not shared with
+// it: built in one helper, this kernel ran the same loops 0.9 % slower on the small-batch score
+// (K = 5, B = 2048, S = 50); as it stands its code is what it was before the helpers.
 template <bool FAST>
 __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_posterior_kernel(GmmArgs a) {
   extern __shared__ float lds[];
@@ -317,16 +328,11 @@ __global__ void __launch_bounds__(kMaxBlock) gaussian_mixture_posterior_kernel(G
     const int nr = (int)min((int64_t)R, a.B - b0);
     wave_stage<false>(yl, a.y + b0 * a.y_bstride, a.y_bstride, nr, Sy, wy, lane);
     wave_lds_sync();
-    if (lane < nr && a.y_mean) {
-      for (int j = 0; j < d; ++j) ys[j] = f_div_acc<FAST>(ys[j] - a.y_mean[j], a.y_std[j]);
-    }
+    if (lane < nr) gmm_normalise_y<FAST>(ys, a);
     float m = -INFINITY, lacc = 0.0f;
     for (int s = 0; s < a.nd; ++s) {
       const float* src = a.t + (int64_t)s * a.ds + b0 * a.rs;
-      if (a.vec4)
-        wave_stage<true>(tl, src, a.rs, nr, S, wt, lane);
-      else
-        wave_stage<false>(tl, src, a.rs, nr, S, wt, lane);
+      gmm_stage_t(tl, a, src, nr, wt, lane);
       wave_lds_sync();
       if (lane < nr) {
         float ml, s0, acc;

@@ -58,8 +58,122 @@ __device__ __forceinline__ float mix_gmax(float v) {
 // Rows a group takes per tile: their loads are issued together (about 8 per lane in flight).
 __host__ __device__ constexpr int mix_rpg(int NV) { return NV >= 8 ? 1 : 8 / NV; }
 
-// LDS: [1 / s_k^2 (M) | -d log|s_k| - 0.5 d log(2 pi) (M) | 1 / s_k (M) | locs transposed (d x M)].
-// The reference's bandwidth can be negative (include/nfn.h): |s| enters the log term only.
+// The per-component constants, staged once per workgroup (ends on the workgroup barrier):
+// [1 / s_k^2 (M) | -d log|s_k| - 0.5 d log(2 pi) (M) | 1 / s_k (M) | locs transposed (d x M)];
+// 1 / s_k is written for the backward only.  The reference's bandwidth can be negative
+// (include/nfn.h): |s| enters the log term only.
+struct MixLds {
+  const float *inv_s2, *lcs, *inv_s, *locT;
+};
+template <bool GRAD>
+__device__ __forceinline__ MixLds mix_stage(float* lds, const MixArgs& a) {
+  const int M = a.M, d = a.d, tid = threadIdx.x;
+  float* inv_s2 = lds;
+  float* lcs = lds + M;
+  float* inv_s = lds + 2 * M;
+  float* locT = lds + 3 * M;
+  for (int k = tid; k < M; k += kMaxBlock) {
+    const double s = (double)a.scales[k];
+    inv_s2[k] = (float)(1.0 / (s * s));
+    lcs[k] = (float)(-(double)d * (log(fabs(s)) + 0.91893853320467274));
+    if constexpr (GRAD) inv_s[k] = (float)(1.0 / s);
+  }
+  for (int i = tid; i < M * d; i += kMaxBlock) {
+    const int k = i / d, j = i - k * d;
+    locT[j * M + k] = a.locs[i];
+  }
+  __syncthreads();
+  return {inv_s2, lcs, inv_s, locT};
+}
+
+// Lane lg's components k = lg + G i: constant over the whole launch.  A slot past M is
+// inactive and reads component 0.
+template <int NV>
+struct MixLane {
+  int kk[NV];
+  bool act[NV];
+  float is2[NV], lc[NV];
+};
+template <int G, int NV>
+__device__ __forceinline__ MixLane<NV> mix_lane(const MixLds& L, int lg, int M) {
+  MixLane<NV> ln;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int k = lg + G * i;
+    ln.act[i] = k < M;
+    ln.kk[i] = ln.act[i] ? k : 0;
+    ln.is2[i] = L.inv_s2[ln.kk[i]];
+    ln.lc[i] = L.lcs[ln.kk[i]];
+  }
+  return ln;
+}
+
+// The kernel term of one row: z2_i = r2_i / s_i^2 and c_i = -0.5 z2_i + lc_i.  y(j) gives the
+// row's raw y_j: how it is loaded is the caller's policy.
+template <bool FAST, int NV, typename Y>
+__device__ __forceinline__ void mix_kernel_term(const MixArgs& a, const MixLds& L, const MixLane<NV>& ln, Y y,
+                                                float (&z2)[NV], float (&c)[NV]) {
+  const int M = a.M;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) z2[i] = 0.0f;
+  for (int j = 0; j < a.d; ++j) {
+    float yj = y(j);
+    if (a.y_mean) yj = f_div<FAST>(yj - a.y_mean[j], a.y_std[j]);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const float dy = yj - L.locT[j * M + ln.kk[i]];
+      z2[i] = fmaf(dy, dy, z2[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    z2[i] *= ln.is2[i];
+    c[i] = fmaf(-0.5f, z2[i], ln.lc[i]);
+  }
+}
+
+// One row's shifted log-sum-exp from the lane's NV logits (-inf in an inactive slot) and NV c
+// values, in two steps: mt = max t, then e0 = exp(t - mt), av = (t - mt) + c, ma = max av,
+// e1 = exp(av - ma), the group sums s0 and s1 of e0 and e1, and lp = (ma + log s1) - log s0 -
+// corr.  The one copy of the row's formula: what a caller does not use falls away after
+// inlining.  The maximum is its own step: the forward takes it as soon as the logits are
+// there, before the kernel term.
+template <int G, int NV>
+__device__ __forceinline__ float mix_row_max(const float (&tv)[NV]) {
+  float mt = tv[0];
+#pragma unroll
+  for (int i = 1; i < NV; ++i) mt = fmaxf(mt, tv[i]);
+  return mix_gmax<G>(mt);
+}
+template <int G, bool FAST, int NV>
+__device__ __forceinline__ void mix_row_lse(const float (&tv)[NV], const float (&c)[NV], float corr, float mt,
+                                            float (&e0)[NV], float (&av)[NV], float& ma, float (&e1)[NV], float& s0,
+                                            float& s1, float& lp) {
+  ma = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    // a lane past M and a -inf logit contribute exactly nothing (no -inf - -inf)
+    const float u = tv[i] == -INFINITY ? -INFINITY : tv[i] - mt;
+    e0[i] = f_exp<FAST>(u);
+    av[i] = u + c[i];
+    ma = fmaxf(ma, av[i]);
+  }
+  ma = mix_gmax<G>(ma);
+  s0 = 0.0f;
+  s1 = 0.0f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    e1[i] = av[i] == -INFINITY ? 0.0f : f_exp<FAST>(av[i] - ma);
+    s0 += e0[i];
+    s1 += e1[i];
+  }
+  s0 = mix_gsum<G>(s0);
+  s1 = mix_gsum<G>(s1);
+  lp = (ma + f_log<FAST>(s1)) - f_log<FAST>(s0) - corr;
+}
+
+// Forward and backward.  Loads are conditional (-inf where the row or the component is past
+// the end), and a row's first y value is loaded with its logits.
 template <int G, int NV, bool FAST, bool GRAD>
 __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
   extern __shared__ float lds[];
@@ -69,38 +183,10 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
   constexpr int ROWS = GPB * RPG;
   const int M = a.M, d = a.d;
   const int tid = threadIdx.x;
-  float* inv_s2 = lds;
-  float* lcs = lds + M;
-  float* inv_s = lds + 2 * M;
-  float* locT = lds + 3 * M;
-  for (int k = tid; k < M; k += kMaxBlock) {
-    const double s = (double)a.scales[k];
-    inv_s2[k] = (float)(1.0 / (s * s));
-    lcs[k] = (float)(-(double)d * (log(fabs(s)) + 0.91893853320467274));
-    inv_s[k] = (float)(1.0 / s);
-  }
-  for (int i = tid; i < M * d; i += kMaxBlock) {
-    const int k = i / d, j = i - k * d;
-    locT[j * M + k] = a.locs[i];
-  }
-  __syncthreads();
-  float corr = 0.0f;
-  if (a.y_mean) {
-    for (int j = 0; j < d; ++j) corr += f_log<FAST>(a.y_std[j]);
-  }
+  const MixLds L = mix_stage<GRAD>(lds, a);
+  const float corr = log_std_sum<FAST>(a.y_mean, a.y_std, d);
   const int lg = tid & (G - 1), grp = tid / G;
-  // this lane's components: constant over the whole launch
-  int kk[NV];
-  bool act[NV];
-  float is2[NV], lc[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int k = lg + G * i;
-    act[i] = k < M;
-    kk[i] = act[i] ? k : 0;
-    is2[i] = inv_s2[kk[i]];
-    lc[i] = lcs[kk[i]];
-  }
+  const MixLane<NV> ln = mix_lane<G, NV>(L, lg, M);
   [[maybe_unused]] float gs[NV];
   if constexpr (GRAD) {
 #pragma unroll
@@ -121,51 +207,19 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
       if constexpr (GRAD) g0[r] = b < a.B ? (a.g_out ? a.g_out[b] : 1.0f) : 0.0f;
 #pragma unroll
       for (int i = 0; i < NV; ++i)
-        tv[r][i] = (b < a.B && act[i]) ? __builtin_nontemporal_load(tr + lg + G * i) : -INFINITY;
+        tv[r][i] = (b < a.B && ln.act[i]) ? __builtin_nontemporal_load(tr + lg + G * i) : -INFINITY;
     }
 #pragma unroll
     for (int r = 0; r < RPG; ++r) {
       const int64_t b = b0 + (int64_t)r * GPB;
       const bool ok = b < a.B;
       const float* yr = a.y + (ok ? b * a.y_bstride : 0);
-      float mt = tv[r][0];
-#pragma unroll
-      for (int i = 1; i < NV; ++i) mt = fmaxf(mt, tv[r][i]);
-      mt = mix_gmax<G>(mt);
-      float z2[NV];
-#pragma unroll
-      for (int i = 0; i < NV; ++i) z2[i] = 0.0f;
-      for (int j = 0; j < d; ++j) {
-        float yj = j == 0 ? y0[r] : yr[j];
-        if (a.y_mean) yj = f_div<FAST>(yj - a.y_mean[j], a.y_std[j]);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-          const float dy = yj - locT[j * M + kk[i]];
-          z2[i] = fmaf(dy, dy, z2[i]);
-        }
-      }
-      float av[NV], e0[NV], e1[NV];
-      float ma = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        z2[i] *= is2[i];
-        // a lane past M and a -inf logit contribute exactly nothing (no -inf - -inf)
-        const float u = tv[r][i] == -INFINITY ? -INFINITY : tv[r][i] - mt;
-        e0[i] = f_exp<FAST>(u);
-        av[i] = u + fmaf(-0.5f, z2[i], lc[i]);
-        ma = fmaxf(ma, av[i]);
-      }
-      ma = mix_gmax<G>(ma);
-      float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        e1[i] = av[i] == -INFINITY ? 0.0f : f_exp<FAST>(av[i] - ma);
-        s0 += e0[i];
-        s1 += e1[i];
-      }
-      s0 = mix_gsum<G>(s0);
-      s1 = mix_gsum<G>(s1);
-      const float lp = (ma + f_log<FAST>(s1)) - f_log<FAST>(s0) - corr;
+      float z2[NV], c[NV], av[NV], e0[NV], e1[NV];
+      float ma, s0, s1, lp;
+      const float mt = mix_row_max<G>(tv[r]);
+      const auto y = [&](int j) { return j == 0 ? y0[r] : yr[j]; };
+      mix_kernel_term<FAST>(a, L, ln, y, z2, c);
+      mix_row_lse<G, FAST>(tv[r], c, corr, mt, e0, av, ma, e1, s0, s1, lp);
       if (ok && lg == 0) {
         if (a.out) a.out[b] = lp;
         acc += (double)lp;
@@ -178,16 +232,16 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
           post[i] = e1[i] * r1;
-          if (ok && act[i]) {
+          if (ok && ln.act[i]) {
             if (a.grad_logits)
               __builtin_nontemporal_store(g * (post[i] - e0[i] * r0), a.grad_logits + b * a.gl_rs + lg + G * i);
             // d/ds_k: post (r2 / s^3 - d / s) = post (z2 - d) / s
-            gs[i] = fmaf(g * post[i], (z2[i] - (float)d) * inv_s[kk[i]], gs[i]);
+            gs[i] = fmaf(g * post[i], (z2[i] - (float)d) * L.inv_s[ln.kk[i]], gs[i]);
           }
         }
         if (a.grad_y) {
           for (int j = 0; j < d; ++j) {
-            float yj = j == 0 ? y0[r] : yr[j];
+            float yj = y(j);
             float sd = 1.0f;
             if (a.y_mean) {
               sd = a.y_std[j];
@@ -195,7 +249,7 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
             }
             float p = 0.0f;
 #pragma unroll
-            for (int i = 0; i < NV; ++i) p = fmaf(post[i] * is2[i], locT[j * M + kk[i]] - yj, p);
+            for (int i = 0; i < NV; ++i) p = fmaf(post[i] * ln.is2[i], L.locT[j * M + ln.kk[i]] - yj, p);
             p = mix_gsum<G>(p);
             if (ok && lg == 0) a.grad_y[b * d + j] = a.y_mean ? f_div<FAST>(g * p, sd) : g * p;
           }
@@ -224,11 +278,11 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_kernel(MixArgs a) {
 }
 
 // The posterior score (BayesianNNEstimator.score, BayesianNNEstimator.py:65-76) of the same
-// layer: logsumexp over a.nd draws of the row's log_prob, minus log S.  The (G, NV) groups
-// and the tiles of kernel_mixture_kernel.  c_bk depends on y_b and the centres only, so a
-// row's NV values per lane are formed once and kept in registers; per draw only the NV
+// layer: logsumexp over a.nd draws of the row's log_prob, minus log S, on the forward's
+// (G, NV) groups and tiles.  c_bk depends on y_b and the centres only, so a row's NV values
+// per lane are formed once (mix_kernel_term) and kept in registers; per draw only the NV
 // logits are loaded, and the next draw's loads are issued before this draw's reductions.
-// Each draw's log_prob is evaluated as the forward evaluates it, operation for operation.
+// Each draw's log_prob is the forward's mix_row_lse.
 template <int G, int NV, bool FAST>
 __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(MixArgs a) {
   extern __shared__ float lds[];
@@ -236,37 +290,12 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(Mix
   constexpr int GPB = kMaxBlock / G;  // groups per workgroup
   constexpr int RPG = mix_rpg(NV);
   constexpr int ROWS = GPB * RPG;
-  const int M = a.M, d = a.d, S = a.nd;
+  const int S = a.nd;
   const int tid = threadIdx.x;
-  float* inv_s2 = lds;
-  float* lcs = lds + M;
-  float* locT = lds + 3 * M;
-  for (int k = tid; k < M; k += kMaxBlock) {
-    const double s = (double)a.scales[k];
-    inv_s2[k] = (float)(1.0 / (s * s));
-    lcs[k] = (float)(-(double)d * (log(fabs(s)) + 0.91893853320467274));
-  }
-  for (int i = tid; i < M * d; i += kMaxBlock) {
-    const int k = i / d, j = i - k * d;
-    locT[j * M + k] = a.locs[i];
-  }
-  __syncthreads();
-  float corr = 0.0f;
-  if (a.y_mean) {
-    for (int j = 0; j < d; ++j) corr += f_log<FAST>(a.y_std[j]);
-  }
+  const MixLds L = mix_stage<false>(lds, a);
+  const float corr = log_std_sum<FAST>(a.y_mean, a.y_std, a.d);
   const int lg = tid & (G - 1), grp = tid / G;
-  int kk[NV];
-  bool act[NV];
-  float is2[NV], lc[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int k = lg + G * i;
-    act[i] = k < M;
-    kk[i] = act[i] ? k : 0;
-    is2[i] = inv_s2[kk[i]];
-    lc[i] = lcs[kk[i]];
-  }
+  const MixLane<NV> ln = mix_lane<G, NV>(L, lg, a.M);
   double acc = 0.0;
   int nfc = 0;
   for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
@@ -281,7 +310,7 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(Mix
       const int64_t b = b0 + (int64_t)r * GPB;
       tr[r] = a.logits + (b < a.B ? b : 0) * a.rs;
 #pragma unroll
-      for (int i = 0; i < NV; ++i) nx[r][i] = __builtin_nontemporal_load(tr[r] + kk[i]);
+      for (int i = 0; i < NV; ++i) nx[r][i] = __builtin_nontemporal_load(tr[r] + ln.kk[i]);
     }
     // the S-independent part: c_k of every row of the tile
     float cv[RPG][NV];
@@ -290,22 +319,7 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(Mix
       const int64_t b = b0 + (int64_t)r * GPB;
       const float* yr = a.y + (b < a.B ? b * a.y_bstride : 0);
       float z2[NV];
-#pragma unroll
-      for (int i = 0; i < NV; ++i) z2[i] = 0.0f;
-      for (int j = 0; j < d; ++j) {
-        float yj = yr[j];
-        if (a.y_mean) yj = f_div<FAST>(yj - a.y_mean[j], a.y_std[j]);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-          const float dy = yj - locT[j * M + kk[i]];
-          z2[i] = fmaf(dy, dy, z2[i]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        z2[i] *= is2[i];
-        cv[r][i] = fmaf(-0.5f, z2[i], lc[i]);
-      }
+      mix_kernel_term<FAST>(a, L, ln, [&](int j) { return yr[j]; }, z2, cv[r]);
     }
     float m[RPG], la[RPG];
 #pragma unroll
@@ -319,42 +333,21 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(Mix
       for (int r = 0; r < RPG; ++r) {
         const bool ok = b0 + (int64_t)r * GPB < a.B;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) tv[r][i] = (ok && act[i]) ? nx[r][i] : -INFINITY;
+        for (int i = 0; i < NV; ++i) tv[r][i] = (ok && ln.act[i]) ? nx[r][i] : -INFINITY;
       }
       if (s + 1 < S) {
 #pragma unroll
         for (int r = 0; r < RPG; ++r) {
           const float* tn = tr[r] + (int64_t)(s + 1) * a.ds;
 #pragma unroll
-          for (int i = 0; i < NV; ++i) nx[r][i] = __builtin_nontemporal_load(tn + kk[i]);
+          for (int i = 0; i < NV; ++i) nx[r][i] = __builtin_nontemporal_load(tn + ln.kk[i]);
         }
       }
 #pragma unroll
       for (int r = 0; r < RPG; ++r) {
-        float mt = tv[r][0];
-#pragma unroll
-        for (int i = 1; i < NV; ++i) mt = fmaxf(mt, tv[r][i]);
-        mt = mix_gmax<G>(mt);
-        float av[NV], e0[NV];
-        float ma = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-          // a lane past M and a -inf logit contribute exactly nothing (no -inf - -inf)
-          const float u = tv[r][i] == -INFINITY ? -INFINITY : tv[r][i] - mt;
-          e0[i] = f_exp<FAST>(u);
-          av[i] = u + cv[r][i];
-          ma = fmaxf(ma, av[i]);
-        }
-        ma = mix_gmax<G>(ma);
-        float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-          s0 += e0[i];
-          s1 += av[i] == -INFINITY ? 0.0f : f_exp<FAST>(av[i] - ma);
-        }
-        s0 = mix_gsum<G>(s0);
-        s1 = mix_gsum<G>(s1);
-        float lp = (ma + f_log<FAST>(s1)) - f_log<FAST>(s0) - corr;
+        float av[NV], e0[NV], e1[NV];
+        float ma, s0, s1, lp;
+        mix_row_lse<G, FAST>(tv[r], cv[r], corr, mix_row_max<G>(tv[r]), e0, av, ma, e1, s0, s1, lp);
         // every logit -inf (s0 is exactly 0 then, and only then): the draw has no component
         // left, its term is -inf and drops out (the single-draw entry gives NaN, -inf - -inf)
         lp = s0 == 0.0f ? -INFINITY : lp;
@@ -375,42 +368,35 @@ __global__ void __launch_bounds__(kMaxBlock) kernel_mixture_posterior_kernel(Mix
   if (a.partials) write_partial(a.partials, acc, nfc, red, a.out_sum, a.epoch);
 }
 
-template <int G, int NV>
-int64_t launch_posterior_one(const MixArgs& a0, size_t lds, hipStream_t s) {
-  MixArgs a = a0;
-  constexpr int ROWS = (kMaxBlock / G) * mix_rpg(NV);
-  a.ntiles = (a.B + ROWS - 1) / ROWS;
-  auto kfn = kernel_mixture_posterior_kernel<G, NV, kFast>;
-  int64_t grid = persistent_grid(kfn, kMaxBlock, lds, a.ntiles);
-  grid = std::max<int64_t>(1, std::min(grid, a.grid_cap));
-  nfn_launch(kfn, dim3((unsigned)grid), dim3(kMaxBlock), (uint32_t)lds, s, a);
-  return grid;
-}
-
-// the (G, NV) instance of launch_shape
-int64_t launch_posterior_shape(const MixArgs& a, size_t lds, hipStream_t s) {
-  const int M = a.M;
-  if (M <= 1) return launch_posterior_one<1, 1>(a, lds, s);
-  if (M <= 2) return launch_posterior_one<2, 1>(a, lds, s);
-  if (M <= 4) return launch_posterior_one<4, 1>(a, lds, s);
-  if (M <= 8) return launch_posterior_one<8, 1>(a, lds, s);
-  if (M <= 16) return launch_posterior_one<16, 1>(a, lds, s);
-  if (M <= 32) return launch_posterior_one<16, 2>(a, lds, s);
-  if (M <= 64) return launch_posterior_one<16, 4>(a, lds, s);
-  if (M <= 128) return launch_posterior_one<16, 8>(a, lds, s);
-  if (M <= 256) return launch_posterior_one<16, 16>(a, lds, s);
-  if (M <= 512) return launch_posterior_one<32, 16>(a, lds, s);
-  if (M <= 1024) return launch_posterior_one<64, 16>(a, lds, s);
+// The (G, NV) instance for M components, handed to f as compile-time constants.  The row
+// reductions cost the same wave instructions whatever G is, so the narrowest group whose
+// lanes can hold the row (<= 16 values each) is the cheapest per row: up to M = 256 a
+// 16-lane group (DPP only, four rows per wave), then 32 and 64 lanes.
+template <int G_, int NV_>
+struct MixShape {
+  static constexpr int G = G_, NV = NV_;
+};
+template <typename F>
+int64_t for_mix_shape(int M, F f) {
+  if (M <= 1) return f(MixShape<1, 1>{});
+  if (M <= 2) return f(MixShape<2, 1>{});
+  if (M <= 4) return f(MixShape<4, 1>{});
+  if (M <= 8) return f(MixShape<8, 1>{});
+  if (M <= 16) return f(MixShape<16, 1>{});
+  if (M <= 32) return f(MixShape<16, 2>{});
+  if (M <= 64) return f(MixShape<16, 4>{});
+  if (M <= 128) return f(MixShape<16, 8>{});
+  if (M <= 256) return f(MixShape<16, 16>{});
+  if (M <= 512) return f(MixShape<32, 16>{});
+  if (M <= 1024) return f(MixShape<64, 16>{});
   return 0;
 }
 
-template <int G, int NV, bool GRAD>
-int64_t launch_one(const MixArgs& a0, size_t lds, hipStream_t s) {
+template <int G, int NV, typename KFN>
+int64_t launch_one(KFN kfn, const MixArgs& a0, size_t lds, hipStream_t s) {
   MixArgs a = a0;
-  if (GRAD) lds = std::max(lds, sizeof(float) * NV * kMaxBlock);  // the grad_scales hand-over reuses the LDS
   constexpr int ROWS = (kMaxBlock / G) * mix_rpg(NV);
   a.ntiles = (a.B + ROWS - 1) / ROWS;
-  auto kfn = kernel_mixture_kernel<G, NV, kFast, GRAD>;
   int64_t grid = persistent_grid(kfn, kMaxBlock, lds, a.ntiles);
   grid = std::max<int64_t>(1, std::min(grid, a.grid_cap));
   nfn_launch(kfn, dim3((unsigned)grid), dim3(kMaxBlock), (uint32_t)lds, s, a);
@@ -419,22 +405,12 @@ int64_t launch_one(const MixArgs& a0, size_t lds, hipStream_t s) {
 
 template <bool GRAD>
 int64_t launch_shape(const MixArgs& a, size_t lds, hipStream_t s) {
-  // The row reductions cost the same wave instructions whatever G is, so the narrowest
-  // group whose lanes can hold the row (<= 16 values each) is the cheapest per row: up to
-  // M = 256 a 16-lane group (DPP only, four rows per wave), then 32 and 64 lanes.
-  const int M = a.M;
-  if (M <= 1) return launch_one<1, 1, GRAD>(a, lds, s);
-  if (M <= 2) return launch_one<2, 1, GRAD>(a, lds, s);
-  if (M <= 4) return launch_one<4, 1, GRAD>(a, lds, s);
-  if (M <= 8) return launch_one<8, 1, GRAD>(a, lds, s);
-  if (M <= 16) return launch_one<16, 1, GRAD>(a, lds, s);
-  if (M <= 32) return launch_one<16, 2, GRAD>(a, lds, s);
-  if (M <= 64) return launch_one<16, 4, GRAD>(a, lds, s);
-  if (M <= 128) return launch_one<16, 8, GRAD>(a, lds, s);
-  if (M <= 256) return launch_one<16, 16, GRAD>(a, lds, s);
-  if (M <= 512) return launch_one<32, 16, GRAD>(a, lds, s);
-  if (M <= 1024) return launch_one<64, 16, GRAD>(a, lds, s);
-  return 0;
+  return for_mix_shape(a.M, [&](auto sh) {
+    constexpr int G = decltype(sh)::G, NV = decltype(sh)::NV;
+    // the grad_scales hand-over reuses the LDS
+    const size_t need = GRAD ? std::max(lds, sizeof(float) * NV * kMaxBlock) : lds;
+    return launch_one<G, NV>(kernel_mixture_kernel<G, NV, kFast, GRAD>, a, need, s);
+  });
 }
 
 }  // namespace
@@ -452,7 +428,10 @@ int64_t launch_mixture_posterior_fast(const MixArgs& a, size_t lds, hipStream_t 
 #else
 int64_t launch_mixture_posterior_precise(const MixArgs& a, size_t lds, hipStream_t s) {
 #endif
-  return launch_posterior_shape(a, lds, s);
+  return for_mix_shape(a.M, [&](auto sh) {
+    constexpr int G = decltype(sh)::G, NV = decltype(sh)::NV;
+    return launch_one<G, NV>(kernel_mixture_posterior_kernel<G, NV, kFast>, a, lds, s);
+  });
 }
 
 }  // namespace nfn

@@ -12,72 +12,23 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import record_parity
 from normalizingflownetwork_amd import GaussianKernelsLayer, KernelMixtureNetwork, ops
 
 import mixture_oracle as MO
+from mixture_cases import (BASE, Kernel, _dev, check_grads, check_op, forward_variants, gradient_walk, nonfinite_rows,
+                           out_sum, stress)
 
 pytestmark = pytest.mark.gpu
 
-BASE = 1e-5
 SHAPES = [(1, 1), (2, 1), (6, 3), (63, 1), (64, 2), (65, 3), (100, 1), (129, 2), (1024, 8)]
 BATCHES = [1, 63, 64, 65, 257, 4099]
 GRAD_BATCHES = [1, 65, 257]
 
 
-def _dev(a):
-    return None if a is None else torch.as_tensor(np.asarray(a, np.float32), device="cuda")
-
-
-def _norm(d):
-    return np.linspace(-0.5, 0.5, d).astype(np.float32), np.linspace(0.5, 2.0, d).astype(np.float32)
-
-
-def _check_forward(what, got, y, t, locs, s, ym=None, ys=None):
-    ref64 = MO.log_prob(y, t, locs, s, ym, ys, np.float64)
-    ref32 = MO.log_prob(y, t, locs, s, ym, ys, np.float32)
-    got = np.asarray(got, np.float64)
-    with np.errstate(invalid="ignore"):
-        err = np.abs(got - ref64)
-    bound = BASE * np.maximum(1.0, np.abs(ref64))
-    record_parity(what, got, ref64, ref32, err, bound)
-    fin = np.isfinite(ref64)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
-    ratio = float((err[fin] / bound[fin]).max()) if fin.any() else 0.0
-    print(f"{what}: max err / bound = {ratio:.3f}")
-    assert ratio <= 1.0, f"{what}: {ratio:.3f} of the bound"
-    return ref64
-
-
-def _forward_variants(tag, y, t, locs, s):
-    """Plain, precise math, y broadcast from one row, logits as a column view, fused y_mean / y_std."""
-    B, M = t.shape
-    d = locs.shape[1]
-    dy, dt, dl, ds = _dev(y), _dev(t), _dev(locs), _dev(s)
-    _check_forward(f"{tag} fast", ops.kernel_mixture_log_prob(dy, dt, dl, ds)[0].cpu().numpy(), y, t, locs, s)
-    prev = ops.set_math_mode("precise")
-    try:
-        got = ops.kernel_mixture_log_prob(dy, dt, dl, ds)[0].cpu().numpy()
-    finally:
-        ops.set_math_mode(prev)
-    _check_forward(f"{tag} precise", got, y, t, locs, s)
-    _check_forward(f"{tag} y-broadcast", ops.kernel_mixture_log_prob(dy[:1], dt, dl, ds)[0].cpu().numpy(),
-                   y[:1], t, locs, s)
-    wide = torch.full((B, M + 5), float("nan"), device="cuda")
-    wide[:, 3:3 + M] = dt
-    view = wide[:, 3:3 + M]
-    assert B == 1 or view.stride(0) == M + 5
-    _check_forward(f"{tag} column-view", ops.kernel_mixture_log_prob(dy, view, dl, ds)[0].cpu().numpy(), y, t, locs, s)
-    ym, ys = _norm(d)
-    _check_forward(f"{tag} fused-norm", ops.kernel_mixture_log_prob(dy, dt, dl, ds, ym, ys)[0].cpu().numpy(),
-                   y, t, locs, s, ym, ys)
-
-
 @pytest.mark.parametrize("M,d", SHAPES)
 @pytest.mark.parametrize("B", BATCHES)
 def test_forward_parity(gpu, B, M, d):
-    y, t, locs, s = MO.make_inputs(B, M, d)
-    _forward_variants(f"mixture B={B} M={M} d={d}", y, t, locs, s)
+    forward_variants(f"mixture B={B} M={M} d={d}", Kernel(B, M, d))
 
 
 @pytest.mark.parametrize("M,d", [(3, 2), (12, 1), (24, 3), (200, 2), (300, 1), (600, 4)])
@@ -85,11 +36,10 @@ def test_every_kernel_instance(gpu, M, d):
     """Component counts that take the (group width, values per lane) instances the shapes above
     do not reach, forward and gradients."""
     B = 65
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=2)
-    _check_forward(f"mixture instance M={M} d={d}",
-                   ops.kernel_mixture_log_prob(_dev(y), _dev(t), _dev(locs), _dev(s))[0].cpu().numpy(), y, t, locs, s)
+    case = Kernel(B, M, d, seed=2)
+    check_op(f"mixture instance M={M} d={d}", case)
     g = np.random.default_rng(M).standard_normal(B).astype(np.float32)
-    _check_grads(f"mixture instance grad M={M} d={d}", y, t, locs, s, g)
+    _check_grads(f"mixture instance grad M={M} d={d}", case, g)
 
 
 STRESS = {"logits20": dict(logit_scale=20.0), "y30": dict(y_scale=30.0)}
@@ -99,13 +49,7 @@ STRESS_SHAPES = [(6, 3), (100, 1), (1024, 8)]
 @pytest.mark.parametrize("M,d", STRESS_SHAPES)
 @pytest.mark.parametrize("kind", ["logits20", "y30", "alternate-minus-inf"])
 def test_forward_stress(gpu, kind, M, d):
-    B = 257
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=3, **STRESS.get(kind, {}))
-    if kind == "alternate-minus-inf":
-        t[:, ::2] = -np.inf  # every other logit removes its component
-    ref = _check_forward(f"mixture stress {kind} M={M} d={d}",
-                         ops.kernel_mixture_log_prob(_dev(y), _dev(t), _dev(locs), _dev(s))[0].cpu().numpy(),
-                         y, t, locs, s)
+    ref = stress(f"mixture stress {kind} M={M} d={d}", Kernel(257, M, d, seed=3, **STRESS.get(kind, {})), kind)
     assert np.isfinite(ref).all()
     if kind == "y30":
         assert np.abs(ref).max() > 1e3
@@ -113,77 +57,33 @@ def test_forward_stress(gpu, kind, M, d):
 
 @pytest.mark.parametrize("M,d", [(6, 3), (100, 1), (129, 2)])
 def test_nonfinite_rows_and_count(gpu, M, d):
-    B = 65
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=4)
-    t[0, :] = -np.inf
-    t[7, M // 2] = np.inf
-    t[64, M - 1] = np.nan
-    out, osum, nf = ops.kernel_mixture_log_prob(_dev(y), _dev(t), _dev(locs), _dev(s), want_nonfinite=True)
-    ref = _check_forward(f"mixture non-finite M={M} d={d}", out.cpu().numpy(), y, t, locs, s)
-    assert list(np.flatnonzero(~np.isfinite(ref))) == [0, 7, 64]
-    assert float(nf.item()) == 3.0
-    assert not np.isfinite(osum.item())
+    case = Kernel(65, M, d, seed=4)
+    case.rows[0, :] = -np.inf
+    case.rows[7, M // 2] = np.inf
+    case.rows[64, M - 1] = np.nan
+    nonfinite_rows(f"mixture non-finite M={M} d={d}", case, [0, 7, 64])
 
 
 @pytest.mark.parametrize("B,M,d", [(65, 6, 3), (4099, 100, 1), (4099, 1024, 8)])
 def test_out_sum(gpu, B, M, d):
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=5)
-    args = (_dev(y), _dev(t), _dev(locs), _dev(s))
-    out, s1, nf = ops.kernel_mixture_log_prob(*args, want_nonfinite=True)
-    want = out.double().cpu().numpy()
-    assert abs(s1.item() - float(np.sum(want))) <= 1e-12 * float(np.abs(want).sum())
-    assert nf.item() == 0.0
-    _, s2, _ = ops.kernel_mixture_log_prob(*args, want_values=False, want_nonfinite=True)
-    assert s1.cpu().numpy().tobytes() == s2.cpu().numpy().tobytes()  # bitwise across runs
+    out_sum(Kernel(B, M, d, seed=5))
 
 
 # --- gradients --------------------------------------------------------------------------
 
-def _grads(y, t, locs, s, g, ym=None, ys=None):
-    lp, gl, gy, gs = ops.kernel_mixture_log_prob_grad(_dev(y), _dev(t), _dev(locs), _dev(s), ym, ys, g_out=_dev(g),
-                                                      want_logp=True)
-    return lp.cpu().numpy(), gl.cpu().numpy(), gy.cpu().numpy(), gs.cpu().numpy()
-
-
-def _check_grads(what, y, t, locs, s, g, ym=None, ys=None, stress=False):
-    lp, gl, gy, gs = _grads(y, t, locs, s, g, ym, ys)
-    r64 = MO.log_prob_grads(y, t, locs, s, g, ym, ys, np.float64)
-    r32 = MO.log_prob_grads(y, t, locs, s, g, ym, ys, np.float32)
-    _check_forward(what + " logp", lp, y, t, locs, s, ym, ys)
-    worst = {}
-    for name, got, ref64, ref32, cond in (("grad_logits", gl, r64[0], r32[0], None), ("grad_y", gy, r64[1], r32[1], None),
-                                          ("grad_scales", gs, r64[2], r32[2], r64[3])):
-        err = np.abs(got.astype(np.float64) - ref64)
-        dev32 = float(np.abs(ref32.astype(np.float64) - ref64).max())
-        if stress:
-            bound = BASE * np.maximum(1.0, np.abs(ref64)) + 4.0 * dev32
-        elif cond is not None:  # a batch sum: judged against its conditioning
-            bound = BASE * np.maximum(1.0, cond)
-        else:
-            bound = BASE * np.maximum(1.0, np.abs(ref64))
-        record_parity(f"{what} {name}", got, ref64, ref32, err, bound, kind="gradient")
-        worst[name] = float((err / bound).max())
-        print(f"{what} {name}: max err / bound = {worst[name]:.3f}; max err = {err.max():.3e}, "
-              f"mirror max dev = {dev32:.3e}, err / mirror dev = {err.max() / max(dev32, 1e-300):.3f}")
-    assert all(v <= 1.0 for v in worst.values()), f"{what}: {worst}"
-    again = _grads(y, t, locs, s, g, ym, ys)
-    assert gs.tobytes() == again[3].tobytes(), "grad_scales differs between two runs"
+def _check_grads(what, case, g, ym=None, ys=None, widened=False):
+    """The shared check, and grad_scales (a batch sum finished in fixed order) bitwise equal
+    between two runs."""
+    gl, gy, gs = check_grads(what, case, g, ym, ys, widened)
+    assert gs.tobytes() == case.grad(g, ym, ys)[3].tobytes(), "grad_scales differs between two runs"
     return gl, gy, gs
 
 
 @pytest.mark.parametrize("M,d", SHAPES)
 @pytest.mark.parametrize("B", GRAD_BATCHES)
 def test_gradient_parity(gpu, B, M, d):
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=6)
     g = np.random.default_rng(B + M).standard_normal(B).astype(np.float32)
-    tag = f"mixture grad B={B} M={M} d={d}"
-    _check_grads(tag, y, t, locs, s, g)
-    _check_grads(tag + " fused-norm", y, t, locs, s, g, *_norm(d))
-    prev = ops.set_math_mode("precise")
-    try:
-        _check_grads(tag + " precise", y, t, locs, s, g)
-    finally:
-        ops.set_math_mode(prev)
+    gradient_walk(f"mixture grad B={B} M={M} d={d}", Kernel(B, M, d, seed=6), g, check=_check_grads)
 
 
 @pytest.mark.parametrize("M,d", STRESS_SHAPES)
@@ -191,19 +91,19 @@ def test_gradient_parity(gpu, B, M, d):
 def test_gradient_stress(gpu, kind, M, d):
     """Gated at 1e-5 max(1, |ref64|) + 4 max|ref32 - ref64| per array (module docstring)."""
     B = 257
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=7, **STRESS[kind])
     g = np.random.default_rng(M).standard_normal(B).astype(np.float32)
-    _check_grads(f"mixture grad stress {kind} M={M} d={d}", y, t, locs, s, g, stress=True)
+    _check_grads(f"mixture grad stress {kind} M={M} d={d}", Kernel(B, M, d, seed=7, **STRESS[kind]), g, widened=True)
 
 
 def test_autograd_matches_grad_entry(gpu):
     B, M, d = 65, 100, 2
-    y, t, locs, s = MO.make_inputs(B, M, d, seed=8)
+    case = Kernel(B, M, d, seed=8)
+    y, t, locs, s = case.y, case.rows, case.locs, case.scales
     g = np.random.default_rng(1).standard_normal(B).astype(np.float32)
     dy, dt, ds = (_dev(a).requires_grad_(True) for a in (y, t, s))
     lp = ops.kernel_mixture_log_prob_diff(dy, dt, _dev(locs), ds)
     (lp * _dev(g)).sum().backward()
-    _, gl, gy, gs = _grads(y, t, locs, s, g)
+    _, gl, gy, gs = case.grad(g)
     np.testing.assert_array_equal(dt.grad.cpu().numpy(), gl)
     np.testing.assert_array_equal(dy.grad.cpu().numpy(), gy)
     np.testing.assert_array_equal(ds.grad.cpu().numpy(), gs)

@@ -19,14 +19,13 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import record_parity
 from normalizingflownetwork_amd import GaussianMixtureLayer, MixtureDensityNetwork, ops
 
 import mdn_oracle as MD
+from mixture_cases import Gmm, _dev, check_grads, forward_variants, gradient_walk, nonfinite_rows, out_sum, stress
 
 pytestmark = pytest.mark.gpu
 
-BASE = 1e-5
 SHAPES = [(1, 1), (2, 1), (5, 1), (2, 3), (5, 3), (21, 1), (22, 1), (85, 1), (86, 1), (52, 2), (171, 1), (93, 5),
           (20, 8), (3, 32), (15, 32), (4, 1), (33, 1)]
 BATCHES = [1, 63, 64, 65, 257, 4099]
@@ -35,74 +34,16 @@ STRESS = {"raw150": dict(raw_scale=150.0), "logits20": dict(logit_scale=20.0), "
           "loc30": dict(loc_scale=30.0)}
 
 
-def _dev(a):
-    return None if a is None else torch.as_tensor(np.asarray(a, np.float32), device="cuda")
-
-
-def _norm(d):
-    return np.linspace(-0.5, 0.5, d).astype(np.float32), np.linspace(0.5, 2.0, d).astype(np.float32)
-
-
-def _check_forward(what, got, y, t, K, d, ym=None, ys=None):
-    ref64 = MD.log_prob(y, t, K, d, ym, ys, np.float64)
-    ref32 = MD.log_prob(y, t, K, d, ym, ys, np.float32)
-    got = np.asarray(got, np.float64)
-    with np.errstate(invalid="ignore"):
-        err = np.abs(got - ref64)
-    bound = BASE * np.maximum(1.0, np.abs(ref64))
-    record_parity(what, got, ref64, ref32, err, bound)
-    fin = np.isfinite(ref64)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
-    ratio = float((err[fin] / bound[fin]).max()) if fin.any() else 0.0
-    print(f"{what}: max err / bound = {ratio:.3f}")
-    assert ratio <= 1.0, f"{what}: {ratio:.3f} of the bound"
-    return ref64
-
-
-def _forward_variants(tag, y, t, K, d):
-    """Fast, precise math, y broadcast from one row, t as a column view, fused y_mean / y_std."""
-    B, P = t.shape
-    dy, dt = _dev(y), _dev(t)
-    _check_forward(f"{tag} fast", ops.gaussian_mixture_log_prob(dy, dt, K, d)[0].cpu().numpy(), y, t, K, d)
-    prev = ops.set_math_mode("precise")
-    try:
-        got = ops.gaussian_mixture_log_prob(dy, dt, K, d)[0].cpu().numpy()
-    finally:
-        ops.set_math_mode(prev)
-    _check_forward(f"{tag} precise", got, y, t, K, d)
-    _check_forward(f"{tag} y-broadcast", ops.gaussian_mixture_log_prob(dy[:1], dt, K, d)[0].cpu().numpy(),
-                   y[:1], t, K, d)
-    wide = torch.full((B, P + 5), float("nan"), device="cuda")
-    wide[:, 3:3 + P] = dt
-    view = wide[:, 3:3 + P]
-    assert B == 1 or view.stride(0) == P + 5
-    _check_forward(f"{tag} column-view", ops.gaussian_mixture_log_prob(dy, view, K, d)[0].cpu().numpy(), y, t, K, d)
-    ym, ys = _norm(d)
-    _check_forward(f"{tag} fused-norm", ops.gaussian_mixture_log_prob(dy, dt, K, d, ym, ys)[0].cpu().numpy(),
-                   y, t, K, d, ym, ys)
-
-
 @pytest.mark.parametrize("K,d", SHAPES)
 @pytest.mark.parametrize("B", BATCHES)
 def test_forward_parity(gpu, B, K, d):
-    y, t = MD.make_inputs(B, K, d)
-    _forward_variants(f"mdn B={B} K={K} d={d}", y, t, K, d)
-
-
-def _alternate_minus_inf(t, K, d):
-    t[:, 2 * K * d::2] = -np.inf  # every other logit removes its component
-    return t
+    forward_variants(f"mdn B={B} K={K} d={d}", Gmm(B, K, d))
 
 
 @pytest.mark.parametrize("K,d", SHAPES)
 @pytest.mark.parametrize("kind", list(STRESS) + ["alternate-minus-inf"])
 def test_forward_stress(gpu, kind, K, d):
-    B = 257
-    y, t = MD.make_inputs(B, K, d, seed=3, **STRESS.get(kind, {}))
-    if kind == "alternate-minus-inf":
-        t = _alternate_minus_inf(t, K, d)
-    ref = _check_forward(f"mdn stress {kind} K={K} d={d}",
-                         ops.gaussian_mixture_log_prob(_dev(y), _dev(t), K, d)[0].cpu().numpy(), y, t, K, d)
+    ref = stress(f"mdn stress {kind} K={K} d={d}", Gmm(257, K, d, seed=3, **STRESS.get(kind, {})), kind)
     if kind == "alternate-minus-inf" and K == 1:
         assert not np.isfinite(ref).any()  # the only component is removed: finiteness still has to agree
     else:
@@ -113,81 +54,28 @@ def test_forward_stress(gpu, kind, K, d):
 
 @pytest.mark.parametrize("K,d", [(6, 3), (85, 1)])
 def test_nonfinite_rows_and_count(gpu, K, d):
-    B = 65
-    y, t = MD.make_inputs(B, K, d, seed=4)
-    lg0 = 2 * K * d
-    t[0, lg0:] = -np.inf
-    t[7, lg0 + K // 2] = np.inf
-    t[64, lg0 + K - 1] = np.nan
-    t[9, 2 * d * (K // 2)] = np.nan  # a loc of component K // 2
-    out, osum, nf = ops.gaussian_mixture_log_prob(_dev(y), _dev(t), K, d, want_nonfinite=True)
-    ref = _check_forward(f"mdn non-finite K={K} d={d}", out.cpu().numpy(), y, t, K, d)
-    assert list(np.flatnonzero(~np.isfinite(ref))) == [0, 7, 9, 64]
-    assert list(np.flatnonzero(~np.isfinite(out.cpu().numpy()))) == [0, 7, 9, 64]
-    assert float(nf.item()) == 4.0
-    assert not np.isfinite(osum.item())
+    case = Gmm(65, K, d, seed=4)
+    lg = case.logits(case.rows)
+    lg[0, :] = -np.inf
+    lg[7, K // 2] = np.inf
+    lg[64, K - 1] = np.nan
+    case.rows[9, 2 * d * (K // 2)] = np.nan  # a loc of component K // 2
+    nonfinite_rows(f"mdn non-finite K={K} d={d}", case, [0, 7, 9, 64])
 
 
 @pytest.mark.parametrize("B,K,d", [(65, 5, 1), (4099, 5, 1), (4099, 93, 5)])
 def test_out_sum(gpu, B, K, d):
-    y, t = MD.make_inputs(B, K, d, seed=5)
-    args = (_dev(y), _dev(t), K, d)
-    out, s1, nf = ops.gaussian_mixture_log_prob(*args, want_nonfinite=True)
-    want = out.double().cpu().numpy()
-    assert abs(s1.item() - float(np.sum(want))) <= 1e-12 * float(np.abs(want).sum())
-    assert nf.item() == 0.0
-    _, s2, _ = ops.gaussian_mixture_log_prob(*args, want_nonfinite=True)
-    assert s1.cpu().numpy().tobytes() == s2.cpu().numpy().tobytes()  # bitwise across runs
-    _, s3, _ = ops.gaussian_mixture_log_prob(*args, want_values=False, want_nonfinite=True)
-    assert s1.cpu().numpy().tobytes() == s3.cpu().numpy().tobytes()  # and without the (B,) output
+    out_sum(Gmm(B, K, d, seed=5))
 
 
 # --- gradients --------------------------------------------------------------------------
-
-def _grads(y, t, K, d, g, ym=None, ys=None):
-    lp, gt, gy = ops.gaussian_mixture_log_prob_grad(_dev(y), _dev(t), K, d, ym, ys, g_out=_dev(g), want_logp=True)
-    return lp.cpu().numpy(), gt.cpu().numpy(), gy.cpu().numpy()
-
-
-def _check_grads(what, y, t, K, d, g, ym=None, ys=None, gated=False):
-    lp, gt, gy = _grads(y, t, K, d, g, ym, ys)
-    r64 = MD.log_prob_grads(y, t, K, d, g, ym, ys, np.float64)
-    r32 = MD.log_prob_grads(y, t, K, d, g, ym, ys, np.float32)
-    _check_forward(what + " logp", lp, y, t, K, d, ym, ys)
-    worst = {}
-    for name, got, ref64, ref32 in (("grad_t", gt, r64[0], r32[0]), ("grad_y", gy, r64[1], r32[1])):
-        assert np.isfinite(ref64).all()
-        assert np.isfinite(got).all(), f"{what} {name}: non-finite gradient"
-        err = np.abs(got.astype(np.float64) - ref64)
-        with np.errstate(invalid="ignore"):
-            dev32 = float(np.nanmax(np.abs(ref32.astype(np.float64) - ref64)))
-        bound = BASE * np.maximum(1.0, np.abs(ref64))
-        plain = float((err / bound).max())
-        if gated:
-            bound = bound + 4.0 * dev32
-        record_parity(f"{what} {name}", got, ref64, ref32, err, bound, kind="gradient")
-        worst[name] = float((err / bound).max())
-        print(f"{what} {name}: max err / bound = {worst[name]:.3f} (/ plain bound = {plain:.3f}); max err = "
-              f"{err.max():.3e}, mirror max dev = {dev32:.3e}, err / mirror dev = {err.max() / max(dev32, 1e-300):.3f}")
-    assert all(v <= 1.0 for v in worst.values()), f"{what}: {worst}"
-    return gt, gy
-
 
 @pytest.mark.parametrize("K,d", SHAPES)
 @pytest.mark.parametrize("B", GRAD_BATCHES)
 def test_gradient_parity(gpu, B, K, d):
     """d <= 8 at the plain bound; the two d = 32 shapes at the gated one (module docstring)."""
-    y, t = MD.make_inputs(B, K, d, seed=6)
     g = np.random.default_rng(B + K).standard_normal(B).astype(np.float32)
-    tag = f"mdn grad B={B} K={K} d={d}"
-    gated = d == 32
-    _check_grads(tag, y, t, K, d, g, gated=gated)
-    _check_grads(tag + " fused-norm", y, t, K, d, g, *_norm(d), gated=gated)
-    prev = ops.set_math_mode("precise")
-    try:
-        _check_grads(tag + " precise", y, t, K, d, g, gated=gated)
-    finally:
-        ops.set_math_mode(prev)
+    gradient_walk(f"mdn grad B={B} K={K} d={d}", Gmm(B, K, d, seed=6), g, widened=d == 32)
 
 
 @pytest.mark.parametrize("K,d", SHAPES)
@@ -195,9 +83,8 @@ def test_gradient_parity(gpu, B, K, d):
 def test_gradient_stress(gpu, kind, K, d):
     """Gated at 1e-5 max(1, |ref64|) + 4 max|ref32 - ref64| per array (module docstring)."""
     B = 257
-    y, t = MD.make_inputs(B, K, d, seed=7, **STRESS[kind])
     g = np.random.default_rng(K).standard_normal(B).astype(np.float32)
-    _check_grads(f"mdn grad stress {kind} K={K} d={d}", y, t, K, d, g, gated=True)
+    check_grads(f"mdn grad stress {kind} K={K} d={d}", Gmm(B, K, d, seed=7, **STRESS[kind]), g, widened=True)
 
 
 @pytest.mark.parametrize("K,d", [(2, 1), (5, 3), (22, 1), (86, 1), (15, 32)])
@@ -205,10 +92,10 @@ def test_gradient_removed_components(gpu, K, d):
     """Alternate -inf logits: every gradient finite, exact zeros in the removed components'
     logit, loc and raw slots."""
     B = 65
-    y, t = MD.make_inputs(B, K, d, seed=8)
-    t = _alternate_minus_inf(t, K, d)
+    case = Gmm(B, K, d, seed=8)
+    case.logits(case.rows)[:, ::2] = -np.inf
     g = np.random.default_rng(K).standard_normal(B).astype(np.float32)
-    gt, gy = _check_grads(f"mdn grad alternate-minus-inf K={K} d={d}", y, t, K, d, g, gated=d == 32)
+    gt, gy = check_grads(f"mdn grad alternate-minus-inf K={K} d={d}", case, g, widened=d == 32)
     assert np.isfinite(gt).all() and np.isfinite(gy).all()
     loc, raw, lg = MD.split(gt, K, d, np.float32)
     assert not loc[:, ::2].any() and not raw[:, ::2].any() and not lg[:, ::2].any()
@@ -218,12 +105,13 @@ def test_gradient_removed_components(gpu, K, d):
 
 def test_autograd_matches_grad_entry(gpu):
     B, K, d = 65, 22, 2
-    y, t = MD.make_inputs(B, K, d, seed=9)
+    case = Gmm(B, K, d, seed=9)
+    y, t = case.y, case.rows
     g = np.random.default_rng(1).standard_normal(B).astype(np.float32)
     dy, dt = (_dev(a).requires_grad_(True) for a in (y, t))
     lp = ops.gaussian_mixture_log_prob_diff(dy, dt, K, d)
     (lp * _dev(g)).sum().backward()
-    _, gt, gy = _grads(y, t, K, d, g)
+    _, gt, gy = case.grad(g)
     np.testing.assert_array_equal(dt.grad.cpu().numpy(), gt)
     np.testing.assert_array_equal(dy.grad.cpu().numpy(), gy)
     # y broadcast from one row: its gradient is the batch sum

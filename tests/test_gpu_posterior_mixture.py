@@ -16,17 +16,18 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import record_parity
 from normalizingflownetwork_amd import (BayesKernelMixtureNetwork, BayesMixtureDensityNetwork, estimators, ops)
 from normalizingflownetwork_amd.scorers import DummySklearWrapper, bayesian_log_likelihood_score
 
 import posterior_mixture_oracle as PO
+from mixture_cases import BASE, Gmm, Kernel, _dev, check, forward_variants, out_sum, refs, stress
 
 pytestmark = pytest.mark.gpu
 
-BASE = 1e-5
 GMM_SHAPES = [(1, 1), (5, 1), (5, 3), (21, 1), (22, 1), (33, 1), (85, 1), (86, 1), (171, 1), (93, 5), (3, 32), (4, 1)]
 KERNEL_SHAPES = [(1, 1), (6, 3), (63, 1), (64, 2), (65, 3), (100, 1), (129, 2), (300, 1), (1024, 8)]
+# the (G, NV) instances of nfn_mixture.hip that KERNEL_SHAPES does not reach: G = 2, G = 4, (16, 1), (16, 2)
+KERNEL_INSTANCES = [(2, 1), (3, 2), (12, 1), (24, 3)]
 # S = 7 for every batch; S in {1, 2, 50} at B = 65 and 257
 SIZES = [(B, 7) for B in (1, 63, 64, 65, 257)] + [(B, S) for B in (65, 257) for S in (1, 2, 50)]
 GMM_STRESS = {"raw150": dict(raw_scale=150.0), "logits20": dict(logit_scale=20.0), "y30": dict(y_scale=30.0),
@@ -34,125 +35,28 @@ GMM_STRESS = {"raw150": dict(raw_scale=150.0), "logits20": dict(logit_scale=20.0
 KERNEL_STRESS = {"logits20": dict(logit_scale=20.0), "y30": dict(y_scale=30.0)}
 
 
-def _dev(a):
-    return None if a is None else torch.as_tensor(np.asarray(a, np.float32), device="cuda")
-
-
-def _norm(d):
-    return np.linspace(-0.5, 0.5, d).astype(np.float32), np.linspace(0.5, 2.0, d).astype(np.float32)
-
-
-class Gmm:
-    """The Gaussian-mixture layer's ops and oracle behind one interface: ``rows`` is (S, B, P)."""
-
-    def __init__(self, S, B, K, d, **scaling):
-        self.K, self.d = K, d
-        self.y, self.rows = PO.make_gmm_inputs(S, B, K, d, **scaling)
-        self.tag = f"gmm posterior B={B} S={S} K={K} d={d}"
-
-    def post(self, y, rows, ym=None, ys=None, **want):
-        return ops.posterior_lse_gaussian_mixture(y, rows, self.K, self.d, ym, ys, **want)
-
-    def single(self, y, rows):
-        return ops.gaussian_mixture_log_prob(y, rows, self.K, self.d)[0]
-
-    def ref(self, y, rows, ym=None, ys=None, dtype=np.float64):
-        return PO.gmm_posterior(y, rows, self.K, self.d, ym, ys, dtype)
-
-    def logits(self, rows):
-        """The view of the logit columns of ``rows``."""
-        return rows[..., 2 * self.K * self.d:]
-
-
-class Kernel:
-    """The kernel-mixture layer's ops and oracle: ``rows`` is (S, B, M)."""
-
-    def __init__(self, S, B, M, d, **scaling):
-        self.M, self.d = M, d
-        self.y, self.rows, self.locs, self.scales = PO.make_kernel_inputs(S, B, M, d, **scaling)
-        self.dl, self.ds = _dev(self.locs), _dev(self.scales)
-        self.tag = f"kernel posterior B={B} S={S} M={M} d={d}"
-
-    def post(self, y, rows, ym=None, ys=None, **want):
-        return ops.posterior_lse_kernel_mixture(y, rows, self.dl, self.ds, ym, ys, **want)
-
-    def single(self, y, rows):
-        return ops.kernel_mixture_log_prob(y, rows, self.dl, self.ds)[0]
-
-    def ref(self, y, rows, ym=None, ys=None, dtype=np.float64):
-        return PO.kernel_posterior(y, rows, self.locs, self.scales, ym, ys, dtype)
-
-    def logits(self, rows):
-        return rows
-
-
-def _check(what, got, ref64, ref32):
-    """tests/test_gpu_mdn.py's ``_check_forward`` against a reference computed once."""
-    got = np.asarray(got, np.float64)
-    with np.errstate(invalid="ignore"):
-        err = np.abs(got - ref64)
-    bound = BASE * np.maximum(1.0, np.abs(ref64))
-    record_parity(what, got, ref64, ref32, err, bound)
-    fin = np.isfinite(ref64)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
-    ratio = float((err[fin] / bound[fin]).max()) if fin.any() else 0.0
-    print(f"{what}: max err / bound = {ratio:.3f}")
-    assert ratio <= 1.0, f"{what}: {ratio:.3f} of the bound"
-
-
-def _refs(case, y, ym=None, ys=None):
-    return case.ref(y, case.rows, ym, ys), case.ref(y, case.rows, ym, ys, np.float32)
-
-
-def _variants(case):
-    """Fast and precise math, y broadcast from one row, the rows as a column view of a wider
-    NaN-filled tensor, fused y_mean / y_std, and a draw stride larger than B * row stride."""
-    y, rows, tag = case.y, case.rows, case.tag
-    S, B, W = rows.shape
-    dy, dr = _dev(y), _dev(rows)
-    r64, r32 = _refs(case, y)
-    _check(f"{tag} fast", case.post(dy, dr)[0].cpu().numpy(), r64, r32)
-    prev = ops.set_math_mode("precise")
-    try:
-        got = case.post(dy, dr)[0].cpu().numpy()
-    finally:
-        ops.set_math_mode(prev)
-    _check(f"{tag} precise", got, r64, r32)
-    wide = torch.full((S, B, W + 5), float("nan"), device="cuda")
-    wide[:, :, 3:3 + W] = dr
-    view = wide[:, :, 3:3 + W]
-    assert (B == 1 or view.stride(1) == W + 5) and (S == 1 or view.stride(0) == B * (W + 5))
-    _check(f"{tag} column-view", case.post(dy, view)[0].cpu().numpy(), r64, r32)
-    tall = torch.full((S, B + 3, W), float("nan"), device="cuda")
-    tall[:, :B] = dr
-    part = tall[:, :B]
-    assert S == 1 or part.stride(0) == (B + 3) * W
-    _check(f"{tag} draw-stride", case.post(dy, part)[0].cpu().numpy(), r64, r32)
-    _check(f"{tag} y-broadcast", case.post(dy[:1], dr)[0].cpu().numpy(), *_refs(case, y[:1]))
-    ym, ys = _norm(case.d)
-    _check(f"{tag} fused-norm", case.post(dy, dr, ym, ys)[0].cpu().numpy(), *_refs(case, y, ym, ys))
-
-
 @pytest.mark.parametrize("K,d", GMM_SHAPES)
 @pytest.mark.parametrize("B,S", SIZES)
 def test_gmm_parity(gpu, B, S, K, d):
-    _variants(Gmm(S, B, K, d))
+    case = Gmm(B, K, d, S)
+    forward_variants(case.tag, case)
 
 
 @pytest.mark.parametrize("M,d", KERNEL_SHAPES)
 @pytest.mark.parametrize("B,S", SIZES)
 def test_kernel_parity(gpu, B, S, M, d):
-    _variants(Kernel(S, B, M, d))
+    case = Kernel(B, M, d, S)
+    forward_variants(case.tag, case)
 
 
 def _single_draw_bitwise(case):
-    """S = 1 without y_mean / y_std: the per-draw term IS the existing computation."""
+    """One draw without y_mean / y_std: the per-draw term IS the forward's computation."""
     dy, dr = _dev(case.y), _dev(case.rows)
     for mode in ("fast", "precise"):
         prev = ops.set_math_mode(mode)
         try:
-            post = case.post(dy, dr)[0].cpu().numpy()
-            single = case.single(dy, dr[0]).cpu().numpy()
+            post = case.op(dy, dr[:1])[0].cpu().numpy()
+            single = case.op(dy, dr[0])[0].cpu().numpy()
         finally:
             ops.set_math_mode(prev)
         assert post.tobytes() == single.tobytes(), f"{case.tag} {mode}"
@@ -161,27 +65,30 @@ def _single_draw_bitwise(case):
 @pytest.mark.parametrize("K,d", GMM_SHAPES)
 @pytest.mark.parametrize("B", [65, 257])
 def test_gmm_single_draw_is_bitwise_the_forward(gpu, B, K, d):
-    _single_draw_bitwise(Gmm(1, B, K, d))
+    _single_draw_bitwise(Gmm(B, K, d, 1))
 
 
 @pytest.mark.parametrize("M,d", KERNEL_SHAPES)
 @pytest.mark.parametrize("B", [65, 257])
 def test_kernel_single_draw_is_bitwise_the_forward(gpu, B, M, d):
-    _single_draw_bitwise(Kernel(1, B, M, d))
+    _single_draw_bitwise(Kernel(B, M, d, 1))
 
 
-def _stress(case, kind):
-    if kind == "alternate-minus-inf":
-        case.logits(case.rows)[..., ::2] = -np.inf  # every other logit removes its component
-    r64, r32 = _refs(case, case.y)
-    _check(f"{case.tag} stress {kind}", case.post(_dev(case.y), _dev(case.rows))[0].cpu().numpy(), r64, r32)
-    return r64
+@pytest.mark.parametrize("M,d", KERNEL_INSTANCES)
+def test_kernel_every_instance(gpu, M, d):
+    """The parity walk and the single-draw bitwise check (on the first of the two draws) on the
+    smallest shapes that take the remaining instances and still straddle a wave tile."""
+    case = Kernel(65, M, d, 2)
+    assert np.isfinite(refs(case, case.y)[0]).all()
+    forward_variants(case.tag, case)
+    _single_draw_bitwise(case)
 
 
 @pytest.mark.parametrize("K,d", GMM_SHAPES)
 @pytest.mark.parametrize("kind", list(GMM_STRESS) + ["alternate-minus-inf"])
 def test_gmm_stress(gpu, kind, K, d):
-    ref = _stress(Gmm(7, 257, K, d, **GMM_STRESS.get(kind, {})), kind)
+    case = Gmm(257, K, d, 7, **GMM_STRESS.get(kind, {}))
+    ref = stress(f"{case.tag} stress {kind}", case, kind)
     if kind == "alternate-minus-inf" and K == 1:
         assert not np.isfinite(ref).any()  # the only component is removed in every draw
     else:
@@ -191,7 +98,8 @@ def test_gmm_stress(gpu, kind, K, d):
 @pytest.mark.parametrize("M,d", KERNEL_SHAPES)
 @pytest.mark.parametrize("kind", list(KERNEL_STRESS) + ["alternate-minus-inf"])
 def test_kernel_stress(gpu, kind, M, d):
-    ref = _stress(Kernel(7, 257, M, d, **KERNEL_STRESS.get(kind, {})), kind)
+    case = Kernel(257, M, d, 7, **KERNEL_STRESS.get(kind, {}))
+    ref = stress(f"{case.tag} stress {kind}", case, kind)
     if kind == "alternate-minus-inf" and M == 1:
         assert not np.isfinite(ref).any()
     else:
@@ -207,7 +115,7 @@ def _nonfinite_inputs(case):
     lg[2, 3, :] = -np.inf
     lg[1, 7, lg.shape[-1] // 2] = np.inf
     lg[3, 64, lg.shape[-1] - 1] = np.nan
-    out, osum, nf = case.post(_dev(case.y), _dev(rows), want_nonfinite=True)
+    out, osum, nf = case.op(_dev(case.y), _dev(rows), want_nonfinite=True)
     got = out.cpu().numpy()
     bad = [int(i) for i in np.flatnonzero(~np.isfinite(got))]
     print(f"{case.tag}: non-finite rows {bad}, values {[float(got[i]) for i in (0, 3, 7, 64)]}, "
@@ -230,53 +138,40 @@ def _nonfinite(case):
     assert np.isfinite(others[0])
     assert abs(float(got[3]) - float(others[0])) <= BASE * max(1.0, abs(float(others[0])))
     rest = np.setdiff1d(np.arange(65), [0, 3])
-    r64, r32 = _refs(case, case.y)
+    r64, r32 = refs(case, case.y)
     assert [int(i) for i in rest[~np.isfinite(r64[rest])]] == [7, 64]
-    _check(f"{case.tag} non-finite", got[rest], r64[rest], r32[rest])
+    check(f"{case.tag} non-finite", got[rest], r64[rest], r32[rest])
 
 
 @pytest.mark.parametrize("K,d", [(6, 3), (85, 1)])
 def test_gmm_nonfinite_draws(gpu, K, d):
-    _nonfinite(Gmm(4, 65, K, d))
+    _nonfinite(Gmm(65, K, d, 4))
 
 
 @pytest.mark.parametrize("M,d", [(6, 3), (100, 1), (129, 2)])
 def test_kernel_nonfinite_draws(gpu, M, d):
-    _nonfinite(Kernel(4, 65, M, d))
-
-
-def _out_sum(case):
-    args = (_dev(case.y), _dev(case.rows))
-    out, s1, nf = case.post(*args, want_nonfinite=True)
-    want = out.double().cpu().numpy()
-    assert abs(s1.item() - float(np.sum(want))) <= 1e-12 * float(np.abs(want).sum())
-    assert nf.item() == 0.0
-    _, s2, _ = case.post(*args, want_nonfinite=True)
-    assert s1.cpu().numpy().tobytes() == s2.cpu().numpy().tobytes()  # bitwise across runs
-    none, s3, _ = case.post(*args, want_values=False, want_nonfinite=True)
-    assert none is None
-    assert s1.cpu().numpy().tobytes() == s3.cpu().numpy().tobytes()  # and without the (B,) output
+    _nonfinite(Kernel(65, M, d, 4))
 
 
 @pytest.mark.parametrize("B,S", [(65, 7), (4099, 3)])
 @pytest.mark.parametrize("K,d", [(5, 1), (93, 5)])
 def test_gmm_out_sum(gpu, B, S, K, d):
-    _out_sum(Gmm(S, B, K, d))
+    out_sum(Gmm(B, K, d, S))
 
 
 @pytest.mark.parametrize("B,S", [(65, 7), (4099, 3)])
 @pytest.mark.parametrize("M,d", [(6, 3), (100, 1), (1024, 8)])
 def test_kernel_out_sum(gpu, B, S, M, d):
-    _out_sum(Kernel(S, B, M, d))
+    out_sum(Kernel(B, M, d, S))
 
 
 def test_layers_dispatch_to_their_ops(gpu):
     from normalizingflownetwork_amd import GaussianKernelsLayer, GaussianMixtureLayer, InverseNormalizingFlowLayer
 
-    case = Gmm(3, 65, 5, 2)
+    case = Gmm(65, 5, 2, 3)
     got = GaussianMixtureLayer(5, 2).posterior_lse(_dev(case.y), _dev(case.rows))[0]
-    assert torch.equal(got, case.post(_dev(case.y), _dev(case.rows))[0])
-    kc = Kernel(3, 65, 6, 2)
+    assert torch.equal(got, case.op(_dev(case.y), _dev(case.rows))[0])
+    kc = Kernel(65, 6, 2, 3)
     layer = GaussianKernelsLayer(3, 2)
     layer.locs = kc.locs
     got, s, nf = layer.posterior_lse(_dev(kc.y), _dev(kc.rows), want_sum=True, want_nonfinite=True)
