@@ -14,6 +14,11 @@ fused backward kernel through the flow chain; the Bayesian
 estimator's variational training (``fit(variational=True)``: weight draw, KL term and their
 gradients) runs in the two fused mean-field kernels.
 
+``fit`` is an epoch loop around one ``_TrainStep`` (device data, generator, Adam, loss, the HIP
+graph captured by ``ops.capture_graph``), which tests and ``tools/bench_variational.py`` build
+too.  What it trains is the object ``_trainables`` hands it: ``_PointWeights`` (the Dense stack's
+weights) or ``_MeanFieldWeights`` (the flat ``loc`` / ``rho`` / prior means of a variational fit).
+
 ``KernelMixtureNetwork`` (``estimators/KernelMixtureNetwork.py``) shares all of it: ``fit``
 dispatches through the density layer (its trainable tensors, its differentiable train-time
 ``log_prob``), so the same loop trains the flow chain or the kernel mixture.
@@ -44,22 +49,32 @@ _ACTIVATIONS = {
 }
 
 
-class _MLP:
-    """Dense stack x -> t (``MaximumLikelihoodNNEstimator.py:37-44``), Glorot-uniform
-    weights and zero biases like Keras' ``Dense`` defaults."""
+def _f32(v):
+    """``v`` as it is when a tensor, else a float32 numpy array."""
+    return v if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
 
-    def __init__(self, n_in: int, hidden_sizes: Sequence[int], n_out: int, activation: str, seed: int):
-        assert type(hidden_sizes) in (tuple, list)
+
+class _MLP:
+    """Dense stack x -> t (``MaximumLikelihoodNNEstimator.py:37-44``) over the given per-layer
+    ``weights`` (in, out) and ``biases``."""
+
+    def __init__(self, weights, biases, activation: str):
         assert activation in _ACTIVATIONS, f"unknown activation {activation!r}"
+        self.weights, self.biases, self.activation = list(weights), list(biases), activation
+        self._device = None
+
+    @classmethod
+    def glorot(cls, n_in: int, hidden_sizes: Sequence[int], n_out: int, activation: str, seed: int):
+        """Glorot-uniform weights and zero biases like Keras' ``Dense`` defaults."""
+        assert type(hidden_sizes) in (tuple, list)
         g = torch.Generator().manual_seed(seed)
         sizes = [n_in] + list(hidden_sizes) + [n_out]
-        self.weights, self.biases = [], []
+        weights, biases = [], []
         for a, b in zip(sizes[:-1], sizes[1:]):
             lim = float(np.sqrt(6.0 / (a + b)))
-            self.weights.append((torch.rand((a, b), generator=g, dtype=torch.float32) * 2 - 1) * lim)
-            self.biases.append(torch.zeros((b,), dtype=torch.float32))
-        self.activation = activation
-        self._device = None
+            weights.append((torch.rand((a, b), generator=g, dtype=torch.float32) * 2 - 1) * lim)
+            biases.append(torch.zeros((b,), dtype=torch.float32))
+        return cls(weights, biases, activation)
 
     def to(self, device):
         if self._device != device:
@@ -68,16 +83,6 @@ class _MLP:
             self._device = device
         return self
 
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        act = _ACTIVATIONS[self.activation]
-        h = x
-        n = len(self.weights)
-        for i, (w, b) in enumerate(zip(self.weights, self.biases)):
-            h = h @ w + b
-            if i < n - 1:
-                h = act(h)
-        return h
-
     def hidden(self, x: torch.Tensor) -> torch.Tensor:
         """Activations entering the linear output layer (the fused Dense path's input)."""
         act = _ACTIVATIONS[self.activation]
@@ -85,6 +90,127 @@ class _MLP:
         for w, b in zip(self.weights[:-1], self.biases[:-1]):
             h = act(h @ w + b)
         return h.contiguous()
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        return self.hidden(x) @ self.weights[-1] + self.biases[-1]
+
+
+class _PointWeights:
+    """What a maximum-likelihood step trains: the weights of ``mlp`` (on the training device), as leaves."""
+
+    draw_size = None  # the step has no weight draw and no penalty term
+
+    def __init__(self, mlp: _MLP):
+        self.mlp = mlp
+        self.parameters = [p.detach().requires_grad_(True) for p in mlp.weights + mlp.biases]
+        nw = len(mlp.weights)
+        mlp.weights, mlp.biases = self.parameters[:nw], self.parameters[nw:]
+
+    def network(self, eps):
+        """``(network, penalty)`` of one step: the x -> t network and what its loss adds to the NLL."""
+        return self.mlp, None
+
+    def finish(self):
+        """Leave the trained values in the estimator."""
+        self.mlp.weights = [p.detach() for p in self.mlp.weights]
+        self.mlp.biases = [p.detach() for p in self.mlp.biases]
+
+
+class _TrainStep:
+    """The training step of ``est`` on the data ``x``, ``y`` (float32 matrices), over the
+    ``trained`` object's parameters plus the density layer's own: the device data, the
+    normalisation, the generator, Adam, the loss and its fp64 epoch sums, and (``capture``) the
+    HIP graph of the full-batch step with its static inputs.  Every N(0, 1) number comes from
+    ``gen`` in one fixed order — per epoch the permutation, per step the x noise, the y noise
+    and the weight draw, each only when in use, by ``randn`` eagerly and by ``normal_`` into the
+    graph's static buffers under replay — so the replayed and the eager loop train identically."""
+
+    def __init__(self, est, x, y, trained, dev):
+        self.est, self.trained, self.dev = est, trained, dev
+        dl, mlp = est.dist_layer, est._mlp
+        # Keras Adam defaults; capturable: step counts and bias corrections live on the device, so the same
+        # optimizer runs eagerly and in the graph.  The layer's own tensors: the kernel mixture's bandwidths
+        self.opt = torch.optim.Adam(trained.parameters + dl.trainable_parameters(dev),
+                                    lr=getattr(est, "learning_rate", 3e-3), betas=(0.9, 0.999), eps=1e-7,
+                                    capturable=True)
+        # the output Dense layer can be fused into the flow chain's kernels only
+        self.fused_dense = (isinstance(dl, InverseNormalizingFlowLayer) and len(mlp.weights) > 1 and est.fused_dense
+                            and ops.dense_fusable(int(mlp.weights[-1].shape[0]), dl.get_total_param_size(), est.n_dims))
+        self.X, self.Y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
+        self.xm, self.xs, self.ym, self.ys = (torch.as_tensor(v, dtype=torch.float32, device=dev)
+                                              for v in (est.x_mean, est.x_std, est.y_mean, est.y_std))
+        self.sum_log_ys = torch.log(self.ys).sum()
+        self.gen = torch.Generator(device=dev).manual_seed(int(est.random_seed))
+        self.acc = torch.zeros((), dtype=torch.float64, device=dev)
+        self.acc_pen = torch.zeros((), dtype=torch.float64, device=dev) if trained.draw_size is not None else None
+        self.graph = None  # ops.CapturedGraph of the full-batch step; idx, noise: its static inputs
+
+    def begin_epoch(self, shuffle: bool) -> torch.Tensor:
+        """The epoch's row order; the epoch sums start again."""
+        n = self.X.shape[0]
+        perm = torch.randperm(n, generator=self.gen, device=self.dev) if shuffle else torch.arange(n, device=self.dev)
+        self.acc.zero_()
+        if self.acc_pen is not None:
+            self.acc_pen.zero_()
+        return perm
+
+    def draws(self, rows: int):
+        """The step's normal draws ``(x noise, y noise, eps)``, in the order the replay refills them."""
+        est, n_eps, gen, dev = self.est, self.trained.draw_size, self.gen, self.dev
+        nx = torch.randn((rows, self.X.shape[1]), generator=gen, device=dev) if est.x_noise_std > 0 else None
+        ny = torch.randn((rows, self.Y.shape[1]), generator=gen, device=dev) if est.y_noise_std > 0 else None
+        eps = torch.randn((n_eps,), generator=gen, device=dev) if n_eps else None
+        return nx, ny, eps
+
+    def loss(self, idx, nx, ny, eps) -> torch.Tensor:
+        """The loss on the rows ``idx`` with the noise draws ``nx`` / ``ny`` and the weight draw
+        ``eps``; its penalty term is added to the epoch's penalty sum."""
+        est, dl = self.est, self.est.dist_layer
+        xn = (self.X[idx] - self.xm) / (self.xs + 1e-8)
+        if nx is not None:
+            xn = xn + est.x_noise_std * nx
+        yc = (self.Y[idx] - self.ym) / self.ys
+        if ny is not None:
+            yc = yc + est.y_noise_std * ny
+        mlp, penalty = self.trained.network(eps)
+        if self.fused_dense:  # output layer fused into the chain, forward and backward
+            lp = ops.log_prob_dense(yc, mlp.hidden(xn), mlp.weights[-1], mlp.biases[-1],
+                                    dl.flow_types, est.n_dims, dl.trainable_base_dist)
+        else:
+            lp = dl.train_log_prob(yc, mlp(xn))  # the layer's differentiable fused log_prob
+        loss = -lp.mean() + self.sum_log_ys
+        if penalty is not None:
+            loss = loss + penalty
+            self.acc_pen.add_(penalty.detach().double() * idx.numel())
+        return loss
+
+    def run(self, idx, nx, ny, eps):
+        """One training step: ``loss``, its gradients (the caller has cleared them) and Adam."""
+        loss = self.loss(idx, nx, ny, eps)
+        loss.backward()
+        self.opt.step()
+        self.acc.add_(loss.detach().double() * idx.numel())
+
+    def capture(self, idx, noise, stream=None):
+        """Capture the step on the batch ``idx`` with its ``draws`` ``noise``, which become the
+        graph's static inputs.  The capture itself executes nothing: this batch then runs as
+        the graph's first replay."""
+        self.idx, self.noise = idx.clone(), noise
+        self.opt.zero_grad(set_to_none=True)
+        self.graph = ops.capture_graph(lambda: self.run(self.idx, *noise), self.dev, stream)
+        self.graph.replay()
+
+    def replay(self, idx):
+        """The captured step on the rows ``idx`` with fresh draws."""
+        self.idx.copy_(idx)
+        for buf in self.noise:
+            if buf is not None:
+                buf.normal_(generator=self.gen)
+        self.graph.replay()
+
+    def epoch_sums(self):
+        """``(loss, penalty | None)`` summed over the rows stepped since ``begin_epoch``."""
+        return float(self.acc.item()), None if self.acc_pen is None else float(self.acc_pen.item())
 
 
 class BaseEstimator:
@@ -113,8 +239,8 @@ class BaseEstimator:
 
     # --- x -> t -----------------------------------------------------------------
     def _build(self, n_dims_x: int):
-        self._mlp = _MLP(n_dims_x, self.hidden_sizes, self.dist_layer.get_total_param_size(), self.activation,
-                         self.random_seed)
+        self._mlp = _MLP.glorot(n_dims_x, self.hidden_sizes, self.dist_layer.get_total_param_size(),
+                                self.activation, self.random_seed)
         if self.x_mean is None:
             self.x_mean = np.zeros((n_dims_x,), np.float32)
             self.x_std = np.ones((n_dims_x,), np.float32)
@@ -131,9 +257,10 @@ class BaseEstimator:
     def set_data_normalization(self, x, y):
         self._assign_data_normalization(x, y)
 
-    def params(self, x) -> torch.Tensor:
-        """``t = MLP((x - mu_x)/(sigma_x + 1e-8))`` (``MaximumLikelihoodNNEstimator.py:40-43``)."""
-        x = ops.as_device_f32(x)
+    def _normalised_x(self, x, device=None) -> torch.Tensor:
+        """``(x - mu_x)/(sigma_x + 1e-8)`` as a (B, n_dims_x) device tensor, with the MLP (built
+        on first use) on the same device."""
+        x = ops.as_device_f32(x, device)
         if x.dim() == 1:
             x = x.unsqueeze(-1)
         if self._mlp is None:
@@ -142,7 +269,12 @@ class BaseEstimator:
         self._mlp.to(dev)
         xm = torch.as_tensor(self.x_mean, dtype=torch.float32, device=dev)
         xs = torch.as_tensor(self.x_std, dtype=torch.float32, device=dev)
-        return self._mlp((x - xm) / (xs + 1e-8)).contiguous()
+        return (x - xm) / (xs + 1e-8)
+
+    def params(self, x) -> torch.Tensor:
+        """``t = MLP((x - mu_x)/(sigma_x + 1e-8))`` (``MaximumLikelihoodNNEstimator.py:40-43``)."""
+        xn = self._normalised_x(x)  # first: it may build the MLP
+        return self._mlp(xn).contiguous()
 
     def __call__(self, x):
         return self.dist_layer(self.params(x))
@@ -154,18 +286,11 @@ class BaseEstimator:
             return None  # the fused Dense kernels evaluate a flow chain
         if torch.is_grad_enabled() and any(w.requires_grad for w in (self._mlp.weights if self._mlp else [])):
             return None
-        x = ops.as_device_f32(x)
-        if x.dim() == 1:
-            x = x.unsqueeze(-1)
-        if self._mlp is None:
-            self._build(int(x.shape[-1]))
-        self._mlp.to(x.device)
+        xn = self._normalised_x(x)
         W, b = self._mlp.weights[-1], self._mlp.biases[-1]
         if not ops.dense_fusable(int(W.shape[0]), int(W.shape[1]), self.n_dims) or len(self._mlp.weights) < 2:
             return None
-        xm = torch.as_tensor(self.x_mean, dtype=torch.float32, device=x.device)
-        xs = torch.as_tensor(self.x_std, dtype=torch.float32, device=x.device)
-        return self._mlp.hidden((x - xm) / (xs + 1e-8)), W, b
+        return self._mlp.hidden(xn), W, b
 
     def call(self, x, training=False):
         return self(x)
@@ -173,8 +298,7 @@ class BaseEstimator:
     # --- evaluation ---------------------------------------------------------------
     def log_pdf(self, x, y):
         """``BaseEstimator.py:77-86``: ``log_prob((y-mu)/sigma) - sum(log sigma)``."""
-        x = np.asarray(x, np.float32) if not isinstance(x, torch.Tensor) else x
-        y = np.asarray(y, np.float32) if not isinstance(y, torch.Tensor) else y
+        x, y = _f32(x), _f32(y)
         assert tuple(x.shape) == tuple(y.shape)
         fused = self._fused_dense_inputs(x)
         if fused is not None:  # output Dense layer fused into the chain kernel
@@ -192,8 +316,7 @@ class BaseEstimator:
 
     def score(self, x_data, y_data) -> float:
         """``BaseEstimator.py:43-47``: mean log-likelihood, reduced on the device in fp64."""
-        x_data = np.asarray(x_data, np.float32) if not isinstance(x_data, torch.Tensor) else x_data
-        y_data = np.asarray(y_data, np.float32) if not isinstance(y_data, torch.Tensor) else y_data
+        x_data, y_data = _f32(x_data), _f32(y_data)
         fused = self._fused_dense_inputs(x_data)
         if fused is not None:  # output Dense layer fused into the chain kernel
             dl = self.dist_layer
@@ -253,8 +376,7 @@ class BaseEstimator:
         data runs as one batch: the MLP in torch, ``log_prob`` in the fused chain kernel on
         the materialised ``t`` (``score`` takes the fused Dense -> chain path: the reference's
         ``score == -evaluate`` tests compare the two)."""
-        x = np.asarray(x, np.float32) if not isinstance(x, torch.Tensor) else x
-        y = np.asarray(y, np.float32) if not isinstance(y, torch.Tensor) else y
+        x, y = _f32(x), _f32(y)
         with torch.no_grad():
             nll = self._get_neg_log_likelihood()(y, self.call(x, training=False))
         return float(nll.double().mean().item())
@@ -285,126 +407,38 @@ class BaseEstimator:
         — the same generator calls in the same order as the eager loop, so both paths train
         identically.  A final partial batch runs eagerly.  Returns ``{"loss": [per-epoch
         mean loss]}``."""
-        x = np.asarray(x, np.float32)
-        y = np.asarray(y, np.float32)
-        assert len(x.shape) == len(y.shape) == 2, "Please pass a matrix not a vector"
-        self._assign_data_normalization(x, y)
-        self._assign_noise_regularisation(n_dims=x.shape[1] + y.shape[1], n_datapoints=x.shape[0])
-        if self._mlp is None:
-            self._build(int(x.shape[1]))
-        dev = ops._device()
-        self._mlp.to(dev)
-        params = self._fit_begin(dev)
-        n_eps = self._fit_draw_size()
-        lr = getattr(self, "learning_rate", 3e-3)
-        dl = self.dist_layer
-        # the layer's own trainable tensors (the kernel mixture's bandwidth variable; a flow
-        # layer has none: everything it evaluates comes out of the MLP)
-        layer_params = dl.trainable_parameters(dev)
-        # Keras Adam defaults; capturable: the step counts and bias corrections live on the
-        # device, so the same optimizer runs eagerly and inside the graph
-        opt = torch.optim.Adam(params + layer_params, lr=lr, betas=(0.9, 0.999), eps=1e-7, capturable=True)
-        P = dl.get_total_param_size()
-        # the output Dense layer can be fused into the flow chain's kernels only
-        fused_dense = (isinstance(dl, InverseNormalizingFlowLayer) and len(self._mlp.weights) > 1
-                       and self.fused_dense
-                       and ops.dense_fusable(int(self._mlp.weights[-1].shape[0]), P, self.n_dims))
+        step = self._train_step(x, y, **kwargs)
+        n = step.X.shape[0]
         batch_size = 32 if batch_size is None else int(batch_size)
         epochs = 1 if epochs is None else int(epochs)
-        X = torch.from_numpy(x).to(dev)
-        Y = torch.from_numpy(y).to(dev)
-        xm, xs = (torch.as_tensor(v, dtype=torch.float32, device=dev) for v in (self.x_mean, self.x_std))
-        ym, ys = (torch.as_tensor(v, dtype=torch.float32, device=dev) for v in (self.y_mean, self.y_std))
-        sum_log_ys = torch.log(ys).sum()
-        gen = torch.Generator(device=dev).manual_seed(int(self.random_seed))
-        n = X.shape[0]
-        acc = torch.zeros((), dtype=torch.float64, device=dev)
-        acc_pen = torch.zeros((), dtype=torch.float64, device=dev) if n_eps is not None else None
-
-        def step(idx, nx, ny, eps):
-            """One training step on the rows ``idx`` with the noise draws ``nx`` / ``ny`` and the
-            weight draw ``eps``."""
-            xn = (X[idx] - xm) / (xs + 1e-8)
-            if nx is not None:
-                xn = xn + self.x_noise_std * nx
-            yc = (Y[idx] - ym) / ys
-            if ny is not None:
-                yc = yc + self.y_noise_std * ny
-            mlp, penalty = self._fit_network(eps)
-            if fused_dense:  # output layer fused into the chain, forward and backward
-                lp = ops.log_prob_dense(yc, mlp.hidden(xn), mlp.weights[-1], mlp.biases[-1],
-                                        dl.flow_types, self.n_dims, dl.trainable_base_dist)
-            else:
-                t = mlp(xn)
-                lp = dl.train_log_prob(yc, t)  # the layer's differentiable fused log_prob
-            loss = -lp.mean() + sum_log_ys
-            if penalty is not None:
-                loss = loss + penalty
-                acc_pen.add_(penalty.detach().double() * idx.numel())
-            loss.backward()
-            opt.step()
-            acc.add_(loss.detach().double() * idx.numel())
-
-        def draws(rows):
-            """The step's normal draws, in the fixed order the replay refills them."""
-            nx = torch.randn((rows, X.shape[1]), generator=gen, device=dev) if self.x_noise_std > 0 else None
-            ny = torch.randn((rows, Y.shape[1]), generator=gen, device=dev) if self.y_noise_std > 0 else None
-            eps = torch.randn((n_eps,), generator=gen, device=dev) if n_eps else None
-            return nx, ny, eps
-
-        graph = None  # (graph, static idx, static draws (x noise, y noise, eps), its pinned workspaces)
         warm = 3  # eager steps before the capture (optimizer state, allocator pools)
         steps_done = 0
-        history = {"loss": []} if acc_pen is None else {"loss": [], "nll": [], "kl": []}
+        history = {"loss": []} if step.acc_pen is None else {"loss": [], "nll": [], "kl": []}
         try:
             for _ in range(epochs):
-                perm = torch.randperm(n, generator=gen, device=dev) if shuffle else torch.arange(n, device=dev)
-                acc.zero_()
-                if acc_pen is not None:
-                    acc_pen.zero_()
+                perm = step.begin_epoch(shuffle)
                 for i in range(0, n, batch_size):
                     idx = perm[i:i + batch_size]
                     full = idx.numel() == batch_size
-                    if use_graph and full and graph is not None:
-                        g_, sidx, static, _ = graph
-                        sidx.copy_(idx)
-                        for buf in static:
-                            if buf is not None:
-                                buf.normal_(generator=gen)
-                        g_.replay()
+                    if use_graph and full and step.graph is not None:
+                        step.replay(idx)
                         continue
-                    noise = draws(idx.numel())
+                    noise = step.draws(idx.numel())
                     if use_graph and full and steps_done >= warm:
-                        # capture the full-batch step (the capture itself executes nothing:
-                        # this batch then runs as the graph's first replay)
-                        sidx = idx.clone()
-                        opt.zero_grad(set_to_none=True)
-                        side = torch.cuda.Stream(device=dev)
-                        side.wait_stream(torch.cuda.current_stream(dev))
-                        g_ = torch.cuda.CUDAGraph()
-                        mark = ops.graph_pin_mark()
-                        with torch.cuda.stream(side):
-                            with torch.cuda.graph(g_, stream=side):
-                                step(sidx, *noise)
-                        torch.cuda.current_stream(dev).wait_stream(side)
-                        # the workspaces the capture pinned live exactly as long as this graph
-                        graph = (g_, sidx, noise, ops.take_graph_workspaces(side, mark))
-                        g_.replay()
+                        step.capture(idx, noise)
                         continue
-                    opt.zero_grad(set_to_none=True)
+                    step.opt.zero_grad(set_to_none=True)
                     if use_graph and steps_done < warm:
-                        side = torch.cuda.Stream(device=dev)  # warm-up on a side stream (capture rules)
-                        side.wait_stream(torch.cuda.current_stream(dev))
-                        with torch.cuda.stream(side):
-                            step(idx, *noise)
-                        torch.cuda.current_stream(dev).wait_stream(side)
+                        with ops.side_stream(step.dev):  # warm-up on a side stream (capture rules)
+                            step.run(idx, *noise)
                     else:
-                        step(idx, *noise)
+                        step.run(idx, *noise)
                     steps_done += 1
-                ep_loss = float(acc.item()) / n
+                loss_sum, pen_sum = step.epoch_sums()
+                ep_loss = loss_sum / n
                 history["loss"].append(ep_loss)
-                if acc_pen is not None:  # loss = nll + kl, the weighted KL term as Keras adds it
-                    ep_kl = float(acc_pen.item()) / n
+                if pen_sum is not None:  # loss = nll + kl, the weighted KL term as Keras adds it
+                    ep_kl = pen_sum / n
                     history["kl"].append(ep_kl)
                     history["nll"].append(ep_loss - ep_kl)
                 if verbose:
@@ -412,32 +446,27 @@ class BaseEstimator:
                 if not np.isfinite(ep_loss):  # tf.keras.callbacks.TerminateOnNaN
                     break
         finally:
-            self._fit_end()
-            dl.finish_training()
+            step.trained.finish()
+            self.dist_layer.finish_training()
         return history
 
-    # --- what a training step trains: the Bayesian estimator's variational fit overrides these
-    def _fit_begin(self, dev) -> list:
-        """The network's trainable tensors (leaves on ``dev``) for the optimizer."""
-        params = [p.detach().requires_grad_(True) for p in self._mlp.weights + self._mlp.biases]
-        nw = len(self._mlp.weights)
-        self._mlp.weights, self._mlp.biases = params[:nw], params[nw:]
-        return params
+    def _train_step(self, x, y, **kwargs) -> _TrainStep:
+        """The step ``fit`` runs on ``x``, ``y``: normalisation and noise scales assigned from the
+        data, the network on the device, and what ``_trainables(dev, **kwargs)`` says to train."""
+        x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+        assert len(x.shape) == len(y.shape) == 2, "Please pass a matrix not a vector"
+        self._assign_data_normalization(x, y)
+        self._assign_noise_regularisation(n_dims=x.shape[1] + y.shape[1], n_datapoints=x.shape[0])
+        if self._mlp is None:
+            self._build(int(x.shape[1]))
+        dev = ops._device()
+        self._mlp.to(dev)
+        return _TrainStep(self, x, y, self._trainables(dev, **kwargs), dev)
 
-    def _fit_draw_size(self) -> Optional[int]:
-        """Length of the N(0, 1) weight draw a step takes after its noise draws; None: the step
-        has no weight draw and no penalty term (0: a penalty, but nothing to draw)."""
-        return None
-
-    def _fit_network(self, eps):
-        """``(network, penalty)`` of one step: the x -> t network to run and the term its loss
-        adds to the batch-mean NLL (None: nothing)."""
-        return self._mlp, None
-
-    def _fit_end(self):
-        """Leave the trained values in the estimator."""
-        self._mlp.weights = [p.detach() for p in self._mlp.weights]
-        self._mlp.biases = [p.detach() for p in self._mlp.biases]
+    def _trainables(self, dev, **kwargs):
+        """What a step trains (``parameters``, ``draw_size``, ``network(eps)``, ``finish()``): here
+        the network's own weights; the Bayesian estimator's variational fit overrides it."""
+        return _PointWeights(self._mlp)
 
 
 class NormalizingFlowNetwork(BaseEstimator):
@@ -463,7 +492,18 @@ class NormalizingFlowNetwork(BaseEstimator):
                                       learning_rate=learning_rate, activation=activation)
 
 
-class KernelMixtureNetwork(BaseEstimator):
+class _CentresFromTargets:
+    """``KernelMixtureNetwork.py:35-39`` / ``BayesKernelMixtureNetwork.py:47-51``: before the
+    training step is set up, the kernel centres are set from the normalised targets."""
+
+    def _train_step(self, x, y, **kwargs):
+        y = np.asarray(y, np.float32)
+        y_circ = (y - np.mean(y, axis=0, dtype=np.float32)) / np.std(y, axis=0, dtype=np.float32)
+        self.dist_layer.set_center_points(y_circ, seed=int(self.random_seed))
+        return super()._train_step(x, y, **kwargs)
+
+
+class KernelMixtureNetwork(_CentresFromTargets, BaseEstimator):
     """``estimators/KernelMixtureNetwork.py``: an MLP whose output is the logit row of a
     mixture of Gaussian kernels at centres fixed from the training targets
     (``GaussianKernelsLayer``), trained by maximum likelihood together with the layer's
@@ -482,15 +522,6 @@ class KernelMixtureNetwork(BaseEstimator):
                        learning_rate=2e-3, activation="relu"):
         return KernelMixtureNetwork(n_dims=n_dims, n_centers=n_centers, hidden_sizes=hidden_sizes,
                                     noise_reg=noise_reg, learning_rate=learning_rate, activation=activation)
-
-    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, **kwargs):
-        """``KernelMixtureNetwork.py:35-39``: the kernel centres are set from the normalised
-        targets, then the MLP and the bandwidth variable train as in ``BaseEstimator.fit``."""
-        y = np.asarray(y, np.float32)
-        y_mean = np.mean(y, axis=0, dtype=np.float32)
-        y_std = np.std(y, axis=0, dtype=np.float32)
-        self.dist_layer.set_center_points((y - y_mean) / y_std, seed=int(self.random_seed))
-        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)
 
 
 class MixtureDensityNetwork(BaseEstimator):
@@ -526,6 +557,46 @@ def mean_field_scale(rho: torch.Tensor) -> torch.Tensor:
 POSTERIOR_CHUNK_BYTES = 256 << 20
 
 
+class _MeanFieldWeights:
+    """What a step of ``BayesianNNEstimator.fit(variational=True)`` trains: the reference's
+    compiled model (``BayesianNNEstimator.py:42-63, 109-146``) on flat vectors.  Per step ONE
+    ``eps ~ N(0, 1)`` for all weights (after the noise draws, from the same generator), the draw
+    ``w = loc + s * eps`` and KL(q || p) in one fused launch (``draw_kl``; backward: one more),
+    the layers' ``W``, ``b`` as views of ``w``, and ``loss = mean NLL + kl_weight_scale * KL`` —
+    Keras adds each layer's ``kl_weight * KL`` to the batch-mean loss, and summing the layers
+    first is the same number.  ``kl_use_exact``, ``prior_scale``, ``trainable_prior`` and
+    ``map_mode`` act as in the reference.  One Adam covers ``loc``, ``rho`` (not in map mode),
+    the prior means (``trainable_prior``) and the density layer's own tensors; the step replays
+    from the same HIP graph, ``eps`` refilled in place.  ``history`` then also holds ``"nll"``
+    and ``"kl"`` (the weighted term), ``"loss"`` being their sum."""
+
+    def __init__(self, est, dev, draw_kl=ops.mean_field_draw_kl_diff):
+        self.est, self.draw_kl = est, draw_kl
+        self.loc, self.rho, self.prior = est._posterior_flat(dev)
+        if self.prior is None and est.trainable_prior:
+            self.prior = torch.zeros_like(self.loc)
+        self.parameters = ([self.loc] + ([] if self.rho is None else [self.rho])
+                           + ([self.prior] if est.trainable_prior else []))
+        for p in self.parameters:
+            p.requires_grad_(True)
+        # length of the N(0, 1) draw a step takes after its noise draws (0, map mode: a penalty, no draw)
+        self.draw_size = 0 if self.rho is None else int(self.loc.numel())
+
+    def network(self, eps):
+        """This step's network, the drawn weights in the Dense stack's shapes, and the weighted KL."""
+        est = self.est
+        w, kl = self.draw_kl(self.loc, self.rho, eps, self.prior, est.prior_scale, est.kl_use_exact)
+        return _MLP(*est._unflatten(w), est.activation), est.kl_weight_scale * kl
+
+    def finish(self):
+        """Write the flat vectors back into the estimator's per-layer layout."""
+        est = self.est
+        est._mlp.weights, est._mlp.biases = est._unflatten(self.loc.detach().clone())
+        if self.rho is not None:
+            est._post_rho = list(zip(*est._unflatten(self.rho.detach().clone())))
+        est._prior_loc = torch.zeros_like(self.loc).detach() if self.prior is None else self.prior.detach()
+
+
 class BayesianNNEstimator(BaseEstimator):
     """Posterior-scoring half of ``estimators/BayesianNNEstimator.py`` for any density layer
     (``dist_layer``: a flow chain, the Gaussian mixture or the kernel mixture).  Every layer
@@ -556,7 +627,6 @@ class BayesianNNEstimator(BaseEstimator):
         self.learning_rate = learning_rate  # BayesianNNEstimator.py:61-63 (Adam(learning_rate))
         self._post_rho = None
         self._prior_loc = None  # flat prior means of every weight, set by a variational fit (None: zeros)
-        self._vi = None         # the flat variational variables while fit(variational=True) runs
         super().__init__(dist_layer, n_dims_x=n_dims_x, hidden_sizes=hidden_sizes, activation=activation,
                          random_seed=random_seed, noise_reg=noise_reg)
         self._draw_gen = None
@@ -608,61 +678,10 @@ class BayesianNNEstimator(BaseEstimator):
         prior = None if self._prior_loc is None else self._prior_loc.detach().to(dev).clone()
         return loc, rho, prior
 
-    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, variational=False, **kwargs):
-        """``BaseEstimator.fit``.  By default the posterior means train by maximum likelihood.
-        ``variational=True`` trains the reference's compiled model (``BayesianNNEstimator.py:
-        42-63, 109-146``): per step ONE ``eps ~ N(0, 1)`` for all weights (after the noise draws,
-        from the same generator), the draw ``w = loc + s * eps`` and KL(q || p) in one fused
-        launch (``ops.mean_field_draw_kl_diff``; backward: one more), the layers' ``W``, ``b`` as
-        views of ``w``, and ``loss = mean NLL + kl_weight_scale * KL`` — Keras adds each layer's
-        ``kl_weight * KL`` to the batch-mean loss, and summing the layers first is the same
-        number.  ``kl_use_exact``, ``prior_scale``, ``trainable_prior`` and ``map_mode`` act as
-        in the reference.  One Adam covers ``loc``, ``rho`` (not in map mode), the prior means
-        (``trainable_prior``) and the density layer's own tensors; the step replays from the same
-        HIP graph, ``eps`` refilled in place.  ``history`` then also holds ``"nll"`` and ``"kl"``
-        (the weighted term), ``"loss"`` being their sum."""
-        self._vi = {} if variational else None
-        try:
-            return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, **kwargs)
-        finally:
-            self._vi = None
-
-    def _fit_begin(self, dev) -> list:
-        if self._vi is None:
-            return super()._fit_begin(dev)
-        loc, rho, prior = self._posterior_flat(dev)
-        if prior is None and self.trainable_prior:
-            prior = torch.zeros_like(loc)
-        train = [loc] + ([] if rho is None else [rho]) + ([prior] if self.trainable_prior else [])
-        for p in train:
-            p.requires_grad_(True)
-        self._vi.update(loc=loc, rho=rho, prior=prior)
-        return train
-
-    def _fit_draw_size(self) -> Optional[int]:
-        if self._vi is None:
-            return None
-        return 0 if self._vi["rho"] is None else int(self._vi["loc"].numel())
-
-    def _fit_network(self, eps):
-        if self._vi is None:
-            return super()._fit_network(eps)
-        v = self._vi
-        w, kl = ops.mean_field_draw_kl_diff(v["loc"], v["rho"], eps, v["prior"], self.prior_scale, self.kl_use_exact)
-        net = _MLP.__new__(_MLP)  # this step's network: the drawn weights in the Dense stack's shapes
-        net.activation = self.activation
-        net.weights, net.biases = self._unflatten(w)
-        return net, self.kl_weight_scale * kl
-
-    def _fit_end(self):
-        if not self._vi:  # maximum likelihood, or a variational fit that failed before it began
-            return super()._fit_end()
-        v = self._vi
-        kernels, biases = self._unflatten(v["loc"].detach().clone())
-        self._mlp.weights, self._mlp.biases = kernels, biases
-        if v["rho"] is not None:
-            self._post_rho = list(zip(*self._unflatten(v["rho"].detach().clone())))
-        self._prior_loc = torch.zeros_like(v["loc"]).detach() if v["prior"] is None else v["prior"].detach()
+    def _trainables(self, dev, variational=False, **kwargs):
+        """``fit(variational=True)`` trains the mean-field posterior (:class:`_MeanFieldWeights`);
+        by default the posterior means train by maximum likelihood."""
+        return _MeanFieldWeights(self, dev) if variational else super()._trainables(dev)
 
     def kl_divergence(self) -> float:
         """Exact ``sum KL(q || p)`` of the current posterior over every weight against the prior
@@ -676,36 +695,28 @@ class BayesianNNEstimator(BaseEstimator):
         """Per posterior draw: the last hidden activations and the sampled output layer,
         ``h (S, B, H)``, ``W (S, H, P)``, ``b (S, P)`` (every layer re-sampled per draw,
         ``BayesianNNEstimator.py:122-145``)."""
-        x = ops.as_device_f32(x)
-        if x.dim() == 1:
-            x = x.unsqueeze(-1)
-        if self._mlp is None:
-            self._build(int(x.shape[-1]))
-        dev = x.device
-        self._mlp.to(dev)
-        if self._draw_gen is None:
-            self._draw_gen = torch.Generator(device=dev).manual_seed(self.random_seed)
-        xm = torch.as_tensor(self.x_mean, dtype=torch.float32, device=dev)
-        xs = torch.as_tensor(self.x_std, dtype=torch.float32, device=dev)
-        xn = (x - xm) / (xs + 1e-8)
-        act = _ACTIVATIONS[self.activation]
+        xn = self._normalised_x(x)
+        dev = xn.device
+        gen = self._draw_generator(dev)
         scales = self.posterior_scales(dev)
         hs, ws, bs = [], [], []
-        n = len(self._mlp.weights)
         for _ in range(n_draws):
-            h = xn
-            for i, (w, b) in enumerate(zip(self._mlp.weights, self._mlp.biases)):
-                if scales is not None:  # a sample of q(w) = N(loc, scale^2), map mode: the mean
-                    sw, sb = scales[i]
-                    w = w + sw * torch.randn(w.shape, generator=self._draw_gen, device=dev, dtype=torch.float32)
-                    b = b + sb * torch.randn(b.shape, generator=self._draw_gen, device=dev, dtype=torch.float32)
-                if i < n - 1:
-                    h = act(h @ w + b)
-                else:
-                    hs.append(h)
-                    ws.append(w)
-                    bs.append(b)
+            net = self._mlp
+            if scales is not None:  # a sample of q(w) = N(loc, scale^2) per layer; map mode: the mean
+                drawn = [(w + sw * torch.randn(w.shape, generator=gen, device=dev, dtype=torch.float32),
+                          b + sb * torch.randn(b.shape, generator=gen, device=dev, dtype=torch.float32))
+                         for w, b, (sw, sb) in zip(net.weights, net.biases, scales)]
+                net = _MLP(*zip(*drawn), self.activation)
+            hs.append(net.hidden(xn))
+            ws.append(net.weights[-1])
+            bs.append(net.biases[-1])
         return torch.stack(hs).contiguous(), torch.stack(ws).contiguous(), torch.stack(bs).contiguous()
+
+    def _draw_generator(self, dev) -> torch.Generator:
+        """The generator of the posterior draws (``_draw_gen``), seeded on first use."""
+        if self._draw_gen is None:
+            self._draw_gen = torch.Generator(device=dev).manual_seed(self.random_seed)
+        return self._draw_gen
 
     def evaluate(self, x, y, batch_size=None, verbose=0, include_kl=False, **kwargs) -> float:
         """Keras ``evaluate`` of ``BayesianNNEstimator``'s compiled loss for ONE posterior
@@ -715,13 +726,10 @@ class BayesianNNEstimator(BaseEstimator):
         ``kl_weight_scale * KL(q || p)``, in the estimator's ``kl_use_exact`` form and, for the
         sampled form, at the very draw the NLL is evaluated at.  Both variants consume the draw
         generator identically."""
-        x = np.asarray(x, np.float32) if not isinstance(x, torch.Tensor) else x
-        y = np.asarray(y, np.float32) if not isinstance(y, torch.Tensor) else y
+        x, y = _f32(x), _f32(y)
         if include_kl:
             dev = ops._device()
-            if self._draw_gen is None:  # as _last_layer_draws creates it
-                self._draw_gen = torch.Generator(device=dev).manual_seed(self.random_seed)
-            before = self._draw_gen.get_state()
+            before = self._draw_generator(dev).get_state()
         with torch.no_grad():
             t = self.params_draws(x, 1)[0]
             nll = self._get_neg_log_likelihood()(y, self.dist_layer(t))
@@ -746,13 +754,17 @@ class BayesianNNEstimator(BaseEstimator):
         h, W, b = self._last_layer_draws(x, n_draws)
         return torch.matmul(h, W) + b[:, None, :]
 
+    def _n_draws(self, n_draws: Optional[int]) -> int:
+        """``BayesianNNEstimator.py:65-76``: 50 posterior draws by default, 1 in map mode."""
+        return n_draws if n_draws is not None else (1 if self.map_mode else 50)
+
     def score(self, x_data, y_data, n_draws: Optional[int] = None) -> float:
         """``BayesianNNEstimator.py:65-76``: 50 draws (1 in map mode).  The S networks are
         drawn once; ``t`` of every draw is formed by the batched library GEMM and scored by the
         layer's fused posterior kernel, in row chunks that keep the (S, rows, P) tensor at or
         under ``POSTERIOR_CHUNK_BYTES``.  The chunks' {sum, non-finite count} pairs are added
         in fp64 on the device."""
-        S = n_draws if n_draws is not None else (1 if self.map_mode else 50)
+        S = self._n_draws(n_draws)
         y = ops.as_device_f32(np.asarray(y_data, np.float32))
         n = int(y.shape[0])
         with torch.no_grad():
@@ -790,8 +802,7 @@ class BayesNormalizingFlowNetwork(BayesianNNEstimator):
         """``BayesianNNEstimator.py:65-76``: 50 draws (1 in map mode).  The output layer is
         fused into the posterior kernel (``nfn_posterior_lse_dense_f32``: t_s = h_s W_s + b_s
         never written to memory) when its width allows, else t is formed by the library GEMM."""
-        S = n_draws if n_draws is not None else (1 if self.map_mode else 50)
-        h, W, b = self._last_layer_draws(np.asarray(x_data, np.float32), S)
+        h, W, b = self._last_layer_draws(np.asarray(x_data, np.float32), self._n_draws(n_draws))
         _, s, nf = ops.posterior_lse_dense(np.asarray(y_data, np.float32), h, W, b, self.dist_layer.flow_types,
                                            self.n_dims, self.dist_layer.trainable_base_dist, self.y_mean,
                                            self.y_std, want_values=False, want_sum=True, want_nonfinite=True)
@@ -803,7 +814,7 @@ class BayesMixtureDensityNetwork(BayesianNNEstimator):
     ``GaussianMixtureLayer``.  ``score`` is the fused posterior kernel
     ``nfn_posterior_lse_gaussian_mixture_f32``.  ``fit`` trains the posterior means by maximum
     likelihood through the fused mixture backward; ``fit(variational=True)`` trains the
-    reference's variational objective (``BayesianNNEstimator.fit``)."""
+    reference's variational objective (``_MeanFieldWeights``)."""
 
     def __init__(self, n_dims, kl_weight_scale, n_centers=5, **kwargs):
         dist_layer = GaussianMixtureLayer(n_centers=n_centers, n_dims=n_dims)
@@ -820,13 +831,13 @@ class BayesMixtureDensityNetwork(BayesianNNEstimator):
                                           prior_scale=prior_scale)
 
 
-class BayesKernelMixtureNetwork(BayesianNNEstimator):
+class BayesKernelMixtureNetwork(_CentresFromTargets, BayesianNNEstimator):
     """``estimators/BayesKernelMixtureNetwork.py``: the Bayesian net over a
     ``GaussianKernelsLayer``.  ``score`` is the fused posterior kernel
-    ``nfn_posterior_lse_kernel_mixture_f32``.  ``fit`` trains the posterior means (and the
-    layer's bandwidth variable) by maximum likelihood through the fused mixture backward;
-    ``fit(variational=True)`` trains the reference's variational objective
-    (``BayesianNNEstimator.fit``)."""
+    ``nfn_posterior_lse_kernel_mixture_f32``.  ``fit`` sets the kernel centres, then trains the
+    posterior means (and the layer's bandwidth variable) by maximum likelihood through the fused
+    mixture backward; ``fit(variational=True)`` trains the reference's variational objective
+    (``_MeanFieldWeights``)."""
 
     def __init__(self, n_dims, kl_weight_scale, n_centers=50, **kwargs):
         dist_layer = GaussianKernelsLayer(n_centers=n_centers, n_dims=n_dims, trainable_scale=True)
@@ -841,13 +852,3 @@ class BayesKernelMixtureNetwork(BayesianNNEstimator):
                                          activation=activation, noise_reg=noise_reg, learning_rate=learning_rate,
                                          trainable_prior=trainable_prior, map_mode=map_mode,
                                          prior_scale=prior_scale)
-
-    def fit(self, x, y, batch_size=None, epochs=None, verbose=1, variational=False, **kwargs):
-        """``BayesKernelMixtureNetwork.py:47-51``: the kernel centres are set from the normalised
-        targets, then the posterior trains as in ``BayesianNNEstimator.fit``."""
-        y = np.asarray(y, np.float32)
-        y_mean = np.mean(y, axis=0, dtype=np.float32)
-        y_std = np.std(y, axis=0, dtype=np.float32)
-        self.dist_layer.set_center_points((y - y_mean) / y_std, seed=int(self.random_seed))
-        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, variational=variational,
-                           **kwargs)

@@ -8,6 +8,7 @@ There is no CPU fallback — without a GPU these raise ``RuntimeError``.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import threading
 from typing import Optional, Sequence
@@ -89,10 +90,11 @@ WORKSPACE_CACHE_ENTRIES = 8
 # was capturing, as (pin sequence number, (device, stream) key, workspace).  A graph's replays
 # write partials and the ticket there, so the block must not go back to the allocator while
 # the graph lives.  Graphs do not tell when they die: an entry stays pinned for the life of
-# the process unless the capturing code takes it over (``graph_pin_mark`` before the capture,
-# ``take_graph_workspaces`` after it) and keeps it next to its graph, as ``estimators.fit``
-# does.  Stream handles are pooled and reused, so a take is scoped by the mark, not only by
-# the stream: pins made before the mark (another live graph's) stay where they are.
+# the process unless the capturing code takes it over and keeps it next to its graph.
+# ``capture_graph`` does that: use it to capture.  Its two primitives (``graph_pin_mark`` before
+# a capture, ``take_graph_workspaces`` after it) are scoped by the mark, not only by the stream,
+# because stream handles are pooled and reused: pins made before the mark (another live
+# graph's) stay where they are.
 _graph_workspaces: list = []
 _pin_seq = 0
 
@@ -117,6 +119,37 @@ def _take_pins(key, since: int) -> list:
     mine = [ws for seq, k, ws in _graph_workspaces if k == key and seq >= since]
     _graph_workspaces[:] = [(seq, k, ws) for seq, k, ws in _graph_workspaces if not (k == key and seq >= since)]
     return mine
+
+
+@contextlib.contextmanager
+def side_stream(device, stream=None):
+    """Run the body on a side stream (``stream``, or a new one) that first waits on the current one, which
+    waits on it afterwards: a step is warmed up and captured off the default stream (capture rules)."""
+    side = torch.cuda.Stream(device=device) if stream is None else stream
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        yield side
+    torch.cuda.current_stream(device).wait_stream(side)
+
+
+class CapturedGraph:
+    """A captured HIP ``graph``, its ``replay()``, and the ``workspaces`` its capture pinned, which
+    live exactly as long as this object."""
+
+    def __init__(self, graph, workspaces: list):
+        self.graph, self.workspaces, self.replay = graph, workspaces, graph.replay
+
+
+def capture_graph(fn, device, stream=None) -> CapturedGraph:
+    """Capture the launches of ``fn()`` on a side stream (``stream``, to share the one a warm-up
+    ran on, or a new one) into a HIP graph, taking over the workspaces the capture pinned.  The
+    capture executes nothing; warming ``fn`` up beforehand is the caller's business."""
+    graph = torch.cuda.CUDAGraph()
+    with side_stream(device, stream) as side:
+        mark = graph_pin_mark()
+        with torch.cuda.graph(graph, stream=side):
+            fn()
+    return CapturedGraph(graph, take_graph_workspaces(side, mark))
 
 
 def _pin(key, ws) -> None:

@@ -8,8 +8,8 @@ import pytest
 import torch
 
 from normalizingflownetwork_amd import (BayesKernelMixtureNetwork, BayesMixtureDensityNetwork,
-                                        BayesNormalizingFlowNetwork, ops)
-from normalizingflownetwork_amd.distribution_layers import InverseNormalizingFlowLayer
+                                        BayesNormalizingFlowNetwork)
+from normalizingflownetwork_amd.estimators import _MeanFieldWeights, _TrainStep
 from oracle import nfn_grad_oracle as G
 
 import mdn_oracle as MD
@@ -69,23 +69,15 @@ def test_one_step_gradients_match_fp64_autograd(gpu, kind, kl_exact, map_mode):
     N = sum(m._layer_sizes())
     m._prior_loc = torch.from_numpy((0.3 * rng.standard_normal(N)).astype(np.float32))
     eps = None if map_mode else torch.from_numpy(rng.standard_normal(N).astype(np.float32)).to(gpu)
-    # the step as fit runs it
-    m._vi = {}
-    train = m._fit_begin(gpu)
-    layer_params = dl.trainable_parameters(gpu)
-    net, penalty = m._fit_network(eps)
-    xd, yd = torch.from_numpy(x).to(gpu), torch.from_numpy(y).to(gpu)
-    if isinstance(dl, InverseNormalizingFlowLayer) and ops.dense_fusable(4, dl.get_total_param_size(), d):
-        lp = ops.log_prob_dense(yd, net.hidden(xd), net.weights[-1], net.biases[-1], dl.flow_types, d,
-                                dl.trainable_base_dist)
-    else:
-        assert kind != "flow"  # hidden (4,) takes the fused Dense path
-        lp = dl.train_log_prob(yd, net(xd))
-    (-lp.mean() + penalty).backward()
-    got = [p.grad.double().cpu() for p in train]
-    loc, rho, prior = (None if v is None else v.detach().cpu().numpy() for v in (m._vi["loc"], m._vi["rho"],
-                                                                               m._vi["prior"]))
-    m._vi = None
+    # the loss of fit's own step (the estimator's normalisation is the identity: mean 0, std 1)
+    trained = _MeanFieldWeights(m, gpu)
+    step = _TrainStep(m, x, y, trained, gpu)
+    assert step.fused_dense == (kind == "flow")  # hidden (4,) takes the fused Dense path
+    step.loss(torch.arange(B, device=gpu), None, None, eps).backward()
+    got = [p.grad.double().cpu() for p in trained.parameters]
+    penalty = step.epoch_sums()[1] / B
+    loc, rho, prior = (None if v is None else v.detach().cpu().numpy()
+                       for v in (trained.loc, trained.rho, trained.prior))
     dl.finish_training()
     # fp64 autograd of the same loss
     f = lambda a: None if a is None else torch.from_numpy(np.asarray(a, np.float64)).requires_grad_(True)
@@ -110,7 +102,7 @@ def test_one_step_gradients_match_fp64_autograd(gpu, kind, kl_exact, map_mode):
                                    MO.log_prob(y, t.detach().numpy(), dl.locs, scales.numpy()), rtol=1e-12)
     (-lp64.mean() + m.kl_weight_scale * terms.sum()).backward()
     kl64 = float(terms.detach().sum())
-    assert abs(float(penalty.detach()) - m.kl_weight_scale * kl64) <= 1e-5 * max(1.0, abs(kl64))
+    assert abs(penalty - m.kl_weight_scale * kl64) <= 1e-5 * max(1.0, abs(kl64))
     ref = [loc64.grad] + ([] if map_mode else [rho64.grad]) + [prior64.grad]
     assert len(got) == len(ref)
     for name, g, r in zip(["loc"] + ([] if map_mode else ["rho"]) + ["prior_loc"], got, ref):

@@ -10,11 +10,12 @@ GPU, in one run:
     gradients out) + 4 with a prior mean (grad_prior_loc is not written) — next to the same
     expressions composed from torch ops.
 (b) The replayed variational training step of ``BayesNormalizingFlowNetwork(1, n_flows=2,
-    hidden_sizes=(10,))`` at batch 32 as ``fit(variational=True)`` captures it (gather,
-    normalisation, draw + KL, MLP, fused log_prob forward and backward, Adam), against the same
-    step whose draw and KL are the torch-op formulation on the same flat vectors.  Both graphs
-    live in this process and are timed alternately, ``--rounds`` windows of ``--steps`` replays
-    each (the ``eps`` refill included, as in ``fit``); the medians are reported.
+    hidden_sizes=(10,))`` at batch 32, the estimator's own ``_TrainStep`` as ``fit(variational=True)``
+    captures it (gather, normalisation, draw + KL, MLP, fused log_prob forward and backward, Adam,
+    the epoch sums), against the same step whose draw and KL are the torch-op formulation on the
+    same flat vectors.  Both graphs live in this process and are timed alternately, ``--rounds``
+    windows of ``--steps`` replays each (the index copy and ``eps`` refill included, as in ``fit``);
+    the medians are reported.
 
 Prints one JSON line per part."""
 
@@ -30,6 +31,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from normalizingflownetwork_amd import BayesNormalizingFlowNetwork, ops  # noqa: E402
+from normalizingflownetwork_amd.estimators import _MeanFieldWeights, _TrainStep  # noqa: E402
 
 HBM_SPEC_BYTES_PER_S = 8e12
 LOG_EXPM1_ONE = float(np.log(np.expm1(1.0)))
@@ -95,64 +97,31 @@ def bench_kernels(N: int, warmup: int, iters: int, dev):
 
 
 class ReplayedStep:
-    """One model's variational training step captured into a HIP graph, built from the
-    estimator's own pieces as ``BaseEstimator.fit`` composes them; ``draw_kl`` is the
-    differentiable draw + KL the step uses."""
+    """One model's variational training step as ``fit(variational=True)`` runs and captures it
+    (the estimator's ``_TrainStep``); ``draw_kl`` is the differentiable draw + KL the step uses."""
 
     def __init__(self, draw_kl, x, y, batch: int, dev):
         m = BayesNormalizingFlowNetwork(1, kl_weight_scale=1.0 / x.shape[0], n_flows=2, hidden_sizes=(10,))
         m._assign_data_normalization(x, y)
         m._build(1)
         m._mlp.to(dev)
-        m._vi = {}
-        self.model, self.draw_kl, dl = m, draw_kl, m.dist_layer
-        params = m._fit_begin(dev) + dl.trainable_parameters(dev)
-        opt = torch.optim.Adam(params, lr=m.learning_rate, betas=(0.9, 0.999), eps=1e-7, capturable=True)
-        X, Y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
-        xm, xs, ym, ys = (torch.as_tensor(v, dtype=torch.float32, device=dev)
-                          for v in (m.x_mean, m.x_std, m.y_mean, m.y_std))
-        sum_log_ys = torch.log(ys).sum()
-        self.gen = torch.Generator(device=dev).manual_seed(22)
-        self.eps = torch.randn((m._fit_draw_size(),), generator=self.gen, device=dev)
-        self.idx = torch.randperm(X.shape[0], generator=self.gen, device=dev)[:batch]
-        self.loss = torch.zeros((), device=dev)
-
-        def step():
-            xn = (X[self.idx] - xm) / (xs + 1e-8)
-            yc = (Y[self.idx] - ym) / ys
-            net, penalty = self._network()
-            loss = -dl.train_log_prob(yc, net(xn)).mean() + sum_log_ys + penalty
-            loss.backward()
-            opt.step()
-            self.loss.copy_(loss.detach())
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+        self.batch = batch
+        self.step = step = _TrainStep(m, x, y, _MeanFieldWeights(m, dev, draw_kl), dev)
+        self.idx = step.begin_epoch(shuffle=True)[:batch]
+        with ops.side_stream(dev) as side:  # fit's three eager steps before the capture
             for _ in range(3):
-                opt.zero_grad(set_to_none=True)
-                step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        opt.zero_grad(set_to_none=True)
-        self.graph = torch.cuda.CUDAGraph()
-        mark = ops.graph_pin_mark()
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(self.graph, stream=side):
-                step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.pins = ops.take_graph_workspaces(side, mark)
-
-    def _network(self):
-        saved = ops.mean_field_draw_kl_diff
-        ops.mean_field_draw_kl_diff = self.draw_kl
-        try:
-            return self.model._fit_network(self.eps)
-        finally:
-            ops.mean_field_draw_kl_diff = saved
+                step.opt.zero_grad(set_to_none=True)
+                step.run(self.idx, *step.draws(batch))
+        step.capture(self.idx, step.draws(batch), stream=side)
 
     def replay(self):
-        self.eps.normal_(generator=self.gen)
-        self.graph.replay()
+        self.step.replay(self.idx)
+
+    def last_loss(self) -> float:
+        """The loss of one more replayed step, from the step's fp64 sum."""
+        before = self.step.epoch_sums()[0]
+        self.replay()
+        return (self.step.epoch_sums()[0] - before) / self.batch
 
 
 def bench_step(rounds: int, steps: int, batch: int, dev):
@@ -178,13 +147,13 @@ def bench_step(rounds: int, steps: int, batch: int, dev):
     med = {k: statistics.median(v) for k, v in times.items()}
     print(json.dumps({
         "tool": "bench_variational", "part": "replayed_step", "model": "BayesNormalizingFlowNetwork(1, n_flows=2, "
-        "hidden_sizes=(10,))", "batch": batch, "weights": int(variants["fused"].eps.numel()), "rounds": rounds,
+        "hidden_sizes=(10,))", "batch": batch, "weights": variants["fused"].step.trained.draw_size, "rounds": rounds,
         "steps_per_round": steps, "fused_us_per_step": round(med["fused"], 2),
         "torch_us_per_step": round(med["torch"], 2),
         "fused_us_min_max": [round(min(times["fused"]), 2), round(max(times["fused"]), 2)],
         "torch_us_min_max": [round(min(times["torch"]), 2), round(max(times["torch"]), 2)],
         "speedup_vs_torch": round(med["torch"] / med["fused"], 3),
-        "final_loss": {k: float(v.loss.item()) for k, v in variants.items()},
+        "final_loss": {k: v.last_loss() for k, v in variants.items()},
     }), flush=True)
 
 
