@@ -27,7 +27,7 @@ DIAG_OUT = os.path.join(PKG_DIR, "libnfn_hip_diag.so")
 ARCH = os.environ.get("NFN_OFFLOAD_ARCH", "gfx950")
 HEADERS = [os.path.join(CSRC, "nfn_device.h"), os.path.join(CSRC, "nfn_launch.h"),
            os.path.join(CSRC, "nfn_grad_device.h"), os.path.join(CSRC, "nfn_bf16.h"),
-           os.path.join(REPO_DIR, "include", "nfn.h")]
+           os.path.join(CSRC, "nfn_dense_device.h"), os.path.join(REPO_DIR, "include", "nfn.h")]
 # (object name, source, extra flags)
 UNITS = [
     ("api", "nfn_api.hip", []),

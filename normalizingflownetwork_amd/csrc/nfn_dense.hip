@@ -4,21 +4,22 @@
 // kernel streams 4H bytes of h per sample instead of the 4P bytes of t
 // (C2 with H = 16: 64 B instead of 128 B).
 //
-// Persistent grid, every wave owns a stream of 64-sample tiles.  Per tile:
-//   1. the tile's h rows (prefetched into registers one tile ahead, non-temporal,
-//      coalesced 16-byte pieces) go to the wave's LDS slot at an odd row stride;
-//   2. the 64 x P tile of t is computed with v_mfma_f32_16x16x4_f32 (exact fp32,
-//      = an fmaf chain): A = h from LDS (lane l: row 16 mt + l % 16, k = 4 ks + l / 16),
-//      B = W from the workgroup's LDS copy, four 16-row M tiles per 16-column N tile;
-//      accumulators + bias are written into the wave's t tile (odd stride);
-//   3. the chain runs per lane exactly as in chain_persistent_kernel.
-#include "nfn_bf16.h"
-#include "nfn_launch.h"
+// Persistent grid, every wave owns a stream of 64-sample tiles.  The per-tile pipeline
+// (h rows to the wave's LDS slot, t = h W + b on v_mfma_f32_16x16x4_f32 into the wave's t
+// tile, the chain per lane) and its pieces are described once in nfn_dense_device.h; the
+// kernels here differ in how the tile's operands arrive and in which chain evaluator runs:
+//   chain_dense_kernel       any d, either math mode, any H: synchronous loads, run-time loops;
+//   chain_dense1_kernel      d = 1, fast math: buffer prefetch one tile ahead, counted waits,
+//                            compile-time QH x NN GEMM, t column-major at kCS (SB: split bf16);
+//   posterior_dense_kernel   the posterior's generality path (synchronous loads);
+//   posterior_dense1_kernel  d = 1: chain_dense1_kernel's pipeline over (tile, draw) units;
+//   posterior_densep_kernel  d >= 2: the same pipeline around the generic chain, t row-major.
+// Only chain_dense1_kernel calls the helpers: the others measured slower or allocated registers
+// differently with them and keep the pipeline in their own text.
+#include "nfn_dense_device.h"
 
 namespace nfn {
 namespace {
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 template <int DM, bool FAST, int NVH>
 __global__ void __launch_bounds__(kMaxBlock) chain_dense_kernel(DenseArgs da) {
@@ -170,7 +171,6 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_kernel(DenseArgs da) {
   __shared__ double red[2 * kMaxBlock / 64];
   constexpr int H = 4 * QH;
   constexpr int RSTEP = 64 / QH;  // h rows per wave-instruction
-  constexpr int kNT = 2;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -225,13 +225,7 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_kernel(DenseArgs da) {
   const int64_t ntiles = a.ntiles;
   const int64_t u0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + wid;
   const int64_t ustep = (int64_t)gridDim.x * (blockDim.x >> 6);
-  const bool norm = a.y_mean != nullptr;
-  float ymean = 0.0f, ystd = 1.0f, corr = 0.0f;
-  if (norm) {
-    ymean = a.y_mean[0];
-    ystd = a.y_std[0];
-    corr = f_log<true>(ystd);
-  }
+  const Norm1 nm = norm1(a);
   const int yoff = lane * (int)a.y_bstride * 4;
   const int hoff = (r0 * (int)hs + 4 * c4) * 4;
   const int kstep = RSTEP * (int)hs * 4;
@@ -239,28 +233,17 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_kernel(DenseArgs da) {
   float ybuf;
   auto issue = [&](int64_t tile) {
     if (diag_ablate_loads(a)) tile = u0;  // diagnostic: compute-only timing (the first tile re-read)
-    const int64_t b0 = tile * 64;
-    const int64_t nr = max((int64_t)0, min((int64_t)64, a.B - b0));
-    const int64_t b0c = nr > 0 ? b0 : 0;
-    const auto ry = tile_rsrc(a.y + b0c * a.y_bstride, nr > 0 ? ((nr - 1) * a.y_bstride + 1) * 4 : 0);
-    ybuf = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, yoff, 0, 0));
-    const auto rh = tile_rsrc(da.h + b0c * hs, nr > 0 ? ((nr - 1) * hs + H) * 4 : 0);
-#pragma unroll
-    for (int k = 0; k < QH; ++k)
-      buf[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, hoff, k * kstep, kNT));
+    const TileSpan sp = tile_span(tile, a.B);
+    ybuf = load_f32(span_y(a, sp, 1), yoff);
+    load_h_rows<QH>(buf, span_h(da, sp, H), hoff, kstep);
   };
   double acc_sum = 0.0;
   int nfc = 0;  // non-finite log_prob values
-  __amdgpu_buffer_rsrc_t pend_r = tile_rsrc(a.out, 0);
-  float pend_v = 0.0f;
-  auto flush = [&]() {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pend_v), pend_r, lane * 4, 0, kNT);
-  };
+  PendingOut pend = pend_none(a);
   issue(u0);
-  flush();  // empty: every path into the loop ends [loads][store] (counted waits)
+  pend_flush(pend, lane);  // empty: every path into the loop ends [loads][store] (counted waits)
   for (int64_t tile = u0; tile < ntiles; tile += ustep) {
-    const int64_t b0 = tile * 64;
-    const int64_t nr = max((int64_t)0, min((int64_t)64, a.B - b0));
+    const TileSpan sp = tile_span(tile, a.B);
     if constexpr (SB) {  // the three bf16 planes of the h tile: row r0 + 16 k, hidden 4 c4 .. 4 c4 + 3
 #pragma unroll
       for (int k = 0; k < QH; ++k) {
@@ -273,19 +256,12 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_kernel(DenseArgs da) {
         *reinterpret_cast<uint2*>(dst + 2 * kSbPlane) = make_uint2(p3[0], p3[1]);
       }
     } else {
-#pragma unroll
-      for (int k = 0; k < QH; ++k) {
-        float* dst = hl + l0 + k * RSTEP * SH;
-        dst[0] = buf[k].x;
-        dst[1] = buf[k].y;
-        dst[2] = buf[k].z;
-        dst[3] = buf[k].w;
-      }
+      store_h_rows<QH>(hl + l0, RSTEP * SH, buf);
     }
-    const float z0 = norm ? f_div<true>(ybuf - ymean, ystd) : ybuf;
+    const float z0 = norm1_z(nm, ybuf);
     wave_lds_sync();
     issue(tile + ustep);
-    flush();
+    pend_flush(pend, lane);
     if constexpr (SB) {
       // A fragments [h3 | h2], [h1 | h1], [h2 | h1]: plane (ak < 2 ? 2 : 1), 0, (ak < 2 ? 1 : 0)
       const uint32_t* pl = reinterpret_cast<const uint32_t*>(hl) + 4 * (ak & 1);
@@ -307,53 +283,32 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_kernel(DenseArgs da) {
 #pragma unroll
       for (int nt = 0; nt < NN; ++nt) {  // every plane read is done: t overlays the planes
         const int n = 16 * nt + am;
-        if (n < P) {
-          const float bn = da.bias ? da.bias[n] : 0.0f;
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-            *reinterpret_cast<f32x4v*>(tl + n * kCS + 16 * mt + 4 * ak) = acc[nt][mt] + bn;
-        }
+        if (n < P) store_t_cols(tl, n, ak, acc[nt], da.bias ? da.bias[n] : 0.0f);
       }
     } else {
-    // t = h W + b on the matrix cores, 16 columns at a time (exact fp32); the A
-    // fragments (4 M tiles x QH k-steps) are shared by every N tile
-    float av[4][QH];
+      // exact fp32; the A fragments are shared by every N tile
+      float av[4][QH];
+      read_a_frags<QH>(av, hl, SH, am, ak);
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int ks = 0; ks < QH; ++ks) av[mt][ks] = hl[(16 * mt + am) * SH + 4 * ks + ak];
-#pragma unroll
-    for (int nt = 0; nt < NN; ++nt) {
-      f32x4v acc[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int ks = 0; ks < QH; ++ks) {
-        const float bv = kBReg ? bvr[kBReg ? ks : 0][kBReg ? nt : 0] : wl[(4 * ks + ak) * NP + 16 * nt + am];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][ks], bv, acc[mt], 0, 0, 0);
+      for (int nt = 0; nt < NN; ++nt) {
+        f32x4v acc[4];
+        t_ntile<QH>(acc, av, [&](int ks) {
+          return kBReg ? bvr[kBReg ? ks : 0][kBReg ? nt : 0] : wl[(4 * ks + ak) * NP + 16 * nt + am];
+        });
+        const int n = 16 * nt + am;
+        if (n < P) store_t_cols(tl, n, ak, acc, da.bias ? da.bias[n] : 0.0f);
       }
-      const int n = 16 * nt + am;
-      if (n < P) {
-        const float bn = da.bias ? da.bias[n] : 0.0f;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-          *reinterpret_cast<f32x4v*>(tl + n * kCS + 16 * mt + 4 * ak) = acc[mt] + bn;
-      }
-    }
     }
     wave_lds_sync();
-    const float lp = (a.prog.K <= 16 ? eval_chain1_fast<true, kCS, CM, false>(z0, tl + lane, a)
-                                     : eval_chain1_fast<false, kCS, kChainLoop, false>(z0, tl + lane, a)) - corr;
-    if (lane < nr) {
+    const float lp = dense1_chain<CM>(z0, tl + lane, a) - nm.corr;
+    if (lane < sp.nr) {
       acc_sum += (double)lp;
       nfc += nonfinite1(lp);
     }
-    pend_v = lp;
-    pend_r = tile_rsrc(a.out && nr > 0 ? a.out + b0 : a.out, a.out ? nr * 4 : 0);
+    pend_set(pend, a, sp, lp);
     wave_lds_sync();  // this tile's LDS reads done before the next tile's writes
   }
-  flush();
+  pend_flush(pend, lane);
   if (a.partials) {
     write_partial(a.partials, acc_sum, nfc, red, a.out_sum, a.epoch, a.pair_base);
   }

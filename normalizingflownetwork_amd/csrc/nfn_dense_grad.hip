@@ -8,15 +8,22 @@
 //   dW = sum_b h_b^T dt_b, db = sum_b dt_b   (MFMA accumulated in registers across the
 //                                        wave's tiles; fixed-order workgroup and grid
 //                                        reductions: bitwise deterministic)
-// Persistent grid, every wave owns a stream of 64-sample tiles; per wave LDS: the h
-// tile (odd stride SH), the t / dt tile (odd stride S) and the flow inputs z_k.
-#include "nfn_grad_device.h"
-#include "nfn_bf16.h"
-#include "nfn_launch.h"
+// Persistent grid, every wave owns a stream of 64-sample tiles.  The front half of a tile —
+// the span and its descriptors, the h prefetch and hand-off, the f32 t GEMM, the chain
+// dispatch, the log_prob / dy stores — is the forward kernel's pipeline, described once in
+// nfn_dense_device.h.  chain_dense1_grad_sb_kernel calls those helpers throughout (its t store
+// apart); chain_dense1_grad_kernel calls them for the memory side only (prefetch, hand-off,
+// normalisation, result stores) and keeps its own A-fragment read, GEMM, t store, chain ladder
+// and epilogue; chain_dense_grad_kernel (run-time H) keeps everything in its own text.  The
+// reasons, with their figures, are in DESIGN.md.  Every kernel owns what follows the chain:
+// the dh and dW / db GEMMs (f32 MFMA, or split bf16 in the SB kernel) and the reductions.
+#include "nfn_dense_device.h"
 
 namespace nfn {
 namespace {
 
+// Any d, either math mode: per wave LDS the h tile (odd stride SH), the t / dt tile (odd
+// stride S) and the flow inputs z_k; synchronous prefetch, run-time H.
 template <int DM, bool FAST, int MH, int NN>
 __global__ void __launch_bounds__(kMaxBlock) chain_dense_grad_kernel(DenseGradArgs g) {
   const DenseArgs& da = g.da;
@@ -226,19 +233,61 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense_grad_kernel(DenseGradAr
   (void)HP;
 }
 
+// The d = 1 backward kernels' epilogue: db's four lanes of a column (ak = 0..3) combined in a
+// fixed order, each wave's [dW | db] into its own LDS region (wfl floats apart), the regions
+// summed in wave order into the workgroup's partial: bitwise deterministic.
+template <int MH, int NN>
+__device__ __forceinline__ void dense1_grad_write_partial(const DenseGradArgs& g, float* lds, int wfl,
+                                                          const f32x4v (&dw)[MH][NN], float (&db)[NN]) {
+  constexpr int H = 16 * MH;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nwave = blockDim.x >> 6;
+  const int am = lane & 15, ak = lane >> 4;
+  const int P = g.da.c.P;
+#pragma unroll
+  for (int nt = 0; nt < NN; ++nt) {
+    db[nt] += __shfl_xor(db[nt], 16);
+    db[nt] += __shfl_xor(db[nt], 32);
+  }
+  const int nWb = H * P + P;
+  __syncthreads();
+  float* mine = lds + wid * wfl;
+#pragma unroll
+  for (int mh = 0; mh < MH; ++mh)
+#pragma unroll
+    for (int nt = 0; nt < NN; ++nt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int hr = 16 * mh + 4 * ak + i, p = 16 * nt + am;  // C layout: row 4 ak + i, column am
+        if (p < P) mine[hr * P + p] = dw[mh][nt][i];
+      }
+#pragma unroll
+  for (int nt = 0; nt < NN; ++nt)
+    if (ak == 0 && 16 * nt + am < P) mine[H * P + 16 * nt + am] = db[nt];
+  __syncthreads();
+  float* out = g.part + (int64_t)blockIdx.x * nWb;
+  for (int i = tid; i < nWb; i += blockDim.x) {
+    float s = lds[i];
+    for (int w = 1; w < nwave; ++w) s += lds[w * wfl + i];
+    out[i] = s;
+  }
+}
+
 // d = 1, fast math, H = 16 MH (MH in {1, 2}), P <= 16 NN: the same backward with
 // every operand placed for the matrix cores and chain_dense1_kernel's memory pipeline.
 // Per 64-sample wave tile (all MFMAs v_mfma_f32_16x16x4_f32, exact fp32):
 //   * h arrives by b128 buffer loads (lane (am, ak): h[16 mt + am][16 j + 4 ak .. + 3])
 //     and goes to LDS (row stride SH = H + 4: conflict-free b128 writes), to be read
-//     back as the A fragments of t = h W (in chain_dense1_kernel's hidden-unit order:
+//     back as the A fragments of t = h W (read_a_frags and t_ntile, the forward kernel's:
 //     t is bitwise the forward kernel's) and, transposed, as those of dW = h^T dt
 //     (contraction over samples in the order s = 16 kq + 4 ak + i, so that dt is read
 //     as b128), kept in registers across the chain; the W fragments of both GEMMs
 //     that read W (t = h W, dh^T = W dt^T) stay in registers for the whole launch;
 //   * t = h W + b leaves the matrix cores as b128 writes into a column-major t tile
 //     (stride kCS, overlaying the dead h rows); the chain backward runs per lane
-//     (grad1_packed on the column stride), turning t into dt in place;
+//     (dense1_grad_chain on the column stride), turning t into dt in place;
 //   * dh^T = W dt^T (contraction over p in the order 16 (ks/4) + 4 ak + ks % 4: the
 //     two 16-lane halves of each ds_read_b32 group land on disjoint banks) — each lane
 //     then holds 4 consecutive hidden units of one sample: dh leaves as b128 stores;
@@ -251,13 +300,13 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense_grad_kernel(DenseGradAr
 // touch of the same operands — the ceiling any faster form of those two GEMMs could reach.
 template <int MH, int NN, int CM = kChainLoop, int AB = 0>
 __global__ void __launch_bounds__(kMaxBlock) chain_dense1_grad_kernel(DenseGradArgs g) {
+  static_assert(CM != kStaticCache && CM != kStaticCacheX, "the parameter-scalar cache is the split-bf16 kernel's");
   const DenseArgs& da = g.da;
   const ChainArgs& a = da.c;
   extern __shared__ float lds[];
   constexpr int H = 16 * MH;
   constexpr int QH = 4 * MH;
   constexpr int SH = H + 4;  // h rows in LDS: 16-byte aligned, == 4 mod 8 (see above)
-  constexpr int kNT = 2;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -292,15 +341,7 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_grad_kernel(DenseGradA
   const int64_t ntiles = a.ntiles;
   const int64_t u0 = (int64_t)blockIdx.x * nwave + wid;
   const int64_t ustep = (int64_t)gridDim.x * nwave;
-  const bool norm = a.y_mean != nullptr;
-  float ymean = 0.0f, ystd = 1.0f, corr = 0.0f;
-  if (norm) {
-    ymean = a.y_mean[0];
-    ystd = a.y_std[0];
-    corr = f_log<true>(ystd);
-  }
-  const bool trainable = a.trainable != 0;
-  const uint32_t types = a.prog.types[0];
+  const Norm1 nm = norm1(a);
   // loop-invariant byte offsets (the host guarantees 64 rows span < 2 GiB)
   const int yoff = lane * (int)a.y_bstride * 4;
   const int hoff = (am * (int)hs + 4 * ak) * 4;      // + mt * 16 rows + j * 16 floats
@@ -310,22 +351,7 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_grad_kernel(DenseGradA
 
   float4 hb[4][MH];
   float ybuf, gbuf;
-  auto issue = [&](int64_t tile) {
-    if (diag_ablate_loads(a)) tile = u0;  // diagnostic: compute-only timing (the first tile re-read)
-    const int64_t b0 = tile * 64;
-    const int64_t nr = max((int64_t)0, min((int64_t)64, a.B - b0));
-    const int64_t b0c = nr > 0 ? b0 : 0;
-    const auto ry = tile_rsrc(a.y + b0c * a.y_bstride, nr > 0 ? ((nr - 1) * a.y_bstride + 1) * 4 : 0);
-    ybuf = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, yoff, 0, 0));
-    const auto rg = tile_rsrc(g.g_out ? g.g_out + b0c : a.y, g.g_out ? nr * 4 : 0);
-    gbuf = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, lane * 4, 0, 0));
-    const auto rh = tile_rsrc(da.h + b0c * hs, nr > 0 ? ((nr - 1) * hs + H) * 4 : 0);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int j = 0; j < MH; ++j)
-        hb[mt][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, hoff, mt * hmt + 64 * j, kNT));
-  };
+  auto issue = [&](int64_t tile) { dense1_grad_issue<MH>(g, tile, u0, lane, yoff, hoff, hmt, ybuf, gbuf, hb); };
 
   f32x4v dw[MH][NN];
   float db[NN];
@@ -338,20 +364,20 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_grad_kernel(DenseGradA
 
   issue(u0);
   for (int64_t tile = u0; tile < ntiles; tile += ustep) {
-    const int64_t b0 = tile * 64;
-    const int64_t nr = max((int64_t)0, min((int64_t)64, a.B - b0));
-    // 1. h rows -> LDS (row-major); read back: the A fragments of t = h W (hidden units
-    // in chain_dense1_kernel's order, so t is bitwise the forward kernel's) and, transposed,
+    const TileSpan sp = tile_span(tile, a.B);
+    const bool trainable = a.trainable != 0;
+    const uint32_t types = a.prog.types[0];
+    const float corr = nm.corr;
+    // 1. h rows -> LDS (row-major); read back: the A fragments of t = h W and, transposed,
     // those of dW (kept in registers across the chain)
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int j = 0; j < MH; ++j)
-        *reinterpret_cast<float4*>(hl + (16 * mt + am) * SH + 16 * j + 4 * ak) = hb[mt][j];
-    const float z0 = norm ? f_div<true>(ybuf - ymean, ystd) : ybuf;
+    store_h_frags<MH>(hl, SH, am, ak, hb);
+    const float z0 = norm1_z(nm, ybuf);
     const float gl = g.g_out ? gbuf : 1.0f;
     wave_lds_sync();
     issue(tile + ustep);  // the next tile's loads (hb is free once in LDS)
+    // The compute side (A fragments, t GEMM and store, chain ladder, epilogue) is this kernel's own text:
+    // with read_a_frags / t_ntile / store_t_cols / dense1_grad_chain / dense1_grad_write_partial the
+    // H = 32 backward ran 0.6 % over the parent's slowest run.
     float av[4][QH], hA[MH][16];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -395,21 +421,12 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_grad_kernel(DenseGradA
       lp = grad1_pairs<kCS>(z, tl + lane, zh, 64, types, K, P, trainable, gl, a.out != nullptr, adj) - corr;
     else
       lp = grad1_packed<kCS>(z, tl + lane, zh, 64, types, K, P, trainable, gl, a.out != nullptr, adj) - corr;
-    if (nr < 64 && lane >= nr) {  // rows past B carry no gradient
-      for (int p = 0; p < P; ++p) tl[p * kCS + lane] = 0.0f;
-    }
-    {
-      const auto ro = tile_rsrc(a.out && nr > 0 ? a.out + b0 : a.out, a.out ? nr * 4 : 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, lp), ro, lane * 4, 0, kNT);
-      const auto rdy = tile_rsrc(g.grad_y && nr > 0 ? g.grad_y + b0 : g.grad_y, g.grad_y ? nr * 4 : 0);
-      const float gy = norm ? f_div<true>(adj, ystd) : adj;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, gy), rdy, lane * 4, 0, kNT);
-    }
+    zero_dt_past_B(tl, P, sp.nr, lane);
+    store_lp_grad_y(g, sp, lane, lp, norm1_dy(nm, adj));
     wave_lds_sync();
     // 4. dh^T = W dt^T: lane (am, ak) ends with dh[16 mt + am][16 mh + 4 ak .. + 3]
     {
-      const auto rdh = tile_rsrc(g.grad_h && nr > 0 ? g.grad_h + b0 * ghs : g.grad_h,
-                                 g.grad_h && nr > 0 ? ((nr - 1) * ghs + H) * 4 : 0);
+      const auto rdh = span_grad_h(g, sp, H);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         float bv[4 * NN];
@@ -428,7 +445,7 @@ __global__ void __launch_bounds__(kMaxBlock) chain_dense1_grad_kernel(DenseGradA
             else
               acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wA[mh][ks], bv[ks], acc, 0, 0, 0);
           }
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, acc), rdh, ghoff, mt * ghmt + 64 * mh, kNT);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, acc), rdh, ghoff, mt * ghmt + 64 * mh, kDenseNT);
         }
       }
     }
@@ -538,12 +555,6 @@ __host__ __device__ inline int dense1_grad_sb_wave_floats(int P, int K) {
 }
 constexpr int kSbWRow = 16;  // dwords per hidden unit of the W parts (16 pairs of p, chunks swizzled as the planes)
 constexpr int kSbWFloats = 3 * 16 * kSbWRow + 32;  // the workgroup's W bf16 parts [part][hidden][pairs of p] and bias
-// The programs the fused Dense backward runs as compile-time blocks with the parameter-scalar
-// cache (SP indexes them): C2's (planar, radial) x 5, and the estimator's default
-// NormalizingFlowNetwork(n_dims, n_flows=10), radial x 10 (NormalizingFlowNetwork.py:10-17).
-constexpr uint32_t kCacheTypes[] = {0x44444u, 0x55555u};
-constexpr int kCacheK[] = {10, 10};
-constexpr int kNumCached = 2;
 
 // CM: the chain form.  The compile-time C2 program (diag kStaticProg, grad1_static) and its
 // parameter-scalar cache (kStaticCache, grad1_static_cache: the release form for C2's program;
@@ -553,6 +564,7 @@ template <int NN, int CM = kChainPairs, int SP = 0>
 __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStaticCacheX || CM == kStaticProg) ? 2 : 3)
     chain_dense1_grad_sb_kernel(DenseGradArgs g) {
   static_assert(NN == 1 || NN == 2, "P <= 32");
+  static_assert(CM < kChainHPair, "no pair forms here (dense1_grad_chain: U = 2 takes grad1_hpairs_regs)");
   const DenseArgs& da = g.da;
   const ChainArgs& a = da.c;
   extern __shared__ float lds[];
@@ -560,7 +572,6 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
   constexpr int QH = 4;
   constexpr int SH = H + 4;  // h rows in LDS (as chain_dense1_grad_kernel)
   constexpr int NP = 16 * NN;
-  constexpr int kNT = 2;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -604,15 +615,7 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
   const int64_t ntiles = a.ntiles;
   const int64_t u0 = (int64_t)blockIdx.x * nwave + wid;
   const int64_t ustep = (int64_t)gridDim.x * nwave;
-  const bool norm = a.y_mean != nullptr;
-  float ymean = 0.0f, ystd = 1.0f, corr = 0.0f;
-  if (norm) {
-    ymean = a.y_mean[0];
-    ystd = a.y_std[0];
-    corr = f_log<true>(ystd);
-  }
-  const bool trainable = a.trainable != 0;
-  const uint32_t types = a.prog.types[0];
+  const Norm1 nm = norm1(a);
   const int yoff = lane * (int)a.y_bstride * 4;
   const int hoff = (am * (int)hs + 4 * ak) * 4;
   const int hmt = 16 * (int)hs * 4;
@@ -623,48 +626,30 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
   const int swz_w = dt_swz(am);  // plane-row reads: rows 16 mt + am share their low 4 bits with am
   const int swz_l = dt_swz(lane);
 
-  float4 hb[4];
+  float4 hb[4][1];
   float ybuf, gbuf;
-  auto issue = [&](int64_t tile) {
-    if (diag_ablate_loads(a)) tile = u0;  // diagnostic: compute-only timing (the first tile re-read)
-    const int64_t b0 = tile * 64;
-    const int64_t nr = max((int64_t)0, min((int64_t)64, a.B - b0));
-    const int64_t b0c = nr > 0 ? b0 : 0;
-    const auto ry = tile_rsrc(a.y + b0c * a.y_bstride, nr > 0 ? ((nr - 1) * a.y_bstride + 1) * 4 : 0);
-    ybuf = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, yoff, 0, 0));
-    const auto rg = tile_rsrc(g.g_out ? g.g_out + b0c : a.y, g.g_out ? nr * 4 : 0);
-    gbuf = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, lane * 4, 0, 0));
-    const auto rh = tile_rsrc(da.h + b0c * hs, nr > 0 ? ((nr - 1) * hs + H) * 4 : 0);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-      hb[mt] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, hoff, mt * hmt, kNT));
-  };
+  auto issue = [&](int64_t tile) { dense1_grad_issue<1>(g, tile, u0, lane, yoff, hoff, hmt, ybuf, gbuf, hb); };
 
-  f32x4v dw[NN];
+  f32x4v dw[1][NN];
   float db[NN];
 #pragma unroll
   for (int nt = 0; nt < NN; ++nt) {
     db[nt] = 0.0f;
-    dw[nt] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    dw[0][nt] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
   }
 
   issue(u0);
   for (int64_t tile = u0; tile < ntiles; tile += ustep) {
-    const int64_t b0 = tile * 64;
-    const int64_t nr = max((int64_t)0, min((int64_t)64, a.B - b0));
+    const TileSpan sp = tile_span(tile, a.B);
     // 1. h rows -> LDS (row-major); read back: t = h W's A fragments and, transposed, dW's
     //    h[sample 32 kc + 16 (j >> 2) + 4 ak + (j & 3)][hidden am] (kept in registers)
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) *reinterpret_cast<float4*>(hl + (16 * mt + am) * SH + 4 * ak) = hb[mt];
-    const float z0 = norm ? f_div<true>(ybuf - ymean, ystd) : ybuf;
+    store_h_frags<1>(hl, SH, am, ak, hb);
+    const float z0 = norm1_z(nm, ybuf);
     const float gl = g.g_out ? gbuf : 1.0f;
     wave_lds_sync();
     issue(tile + ustep);  // the next tile's loads (hb is free once in LDS)
     float av[4][QH], hA[16];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int ks = 0; ks < QH; ++ks) av[mt][ks] = hl[(16 * mt + am) * SH + 4 * ks + ak];
+    read_a_frags<QH>(av, hl, SH, am, ak);
 #pragma unroll
     for (int j = 0; j < 16; ++j) hA[j] = hl[(32 * (j >> 3) + 16 * ((j >> 2) & 1) + 4 * ak + (j & 3)) * SH + am];
     wave_lds_sync();  // every h read done before the t tile overwrites the rows
@@ -672,14 +657,8 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
 #pragma unroll
     for (int nt = 0; nt < NN; ++nt) {
       f32x4v acc[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int ks = 0; ks < QH; ++ks)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-          acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][ks], wB[ks][nt], acc[mt], 0, 0, 0);
-      if (16 * nt + am < P) {
+      t_ntile<QH>(acc, av, [&](int ks) { return wB[ks][nt]; });
+      if (16 * nt + am < P) {  // own text: the bias is re-read from LDS for every M tile, as the parent's code did
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
           *reinterpret_cast<f32x4v*>(tl + (16 * nt + am) * kCS + 16 * mt + 4 * ak) = acc[mt] + bl[16 * nt + am];
@@ -688,32 +667,11 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
     wave_lds_sync();
     // 3. the chain forward + reverse per lane: the t column entries become g * d logp / d t
     float adj, z = z0;
-    float lp;
-    if constexpr (CM == kStaticCache || CM == kStaticCacheX)
-      lp = grad1_static_cache<kCacheTypes[SP], kCacheK[SP], kCS, CM == kStaticCache>(z, tl + lane, P, trainable, gl,
-                                                                                      a.out != nullptr, adj) - corr;
-    else if constexpr (CM == kStaticProg)
-      lp = grad1_static<kStaticTypes[0], kStaticK[0], kCS>(z, tl + lane, zh, 64, P, trainable, gl, a.out != nullptr,
-                                                            adj) - corr;
-    else if constexpr (CM >= kChainHPair)
-      lp = grad1_hpairs<((CM - kChainHPair) % 9) / 3, (CM - kChainHPair) % 3, kCS>(
-               z, tl + lane, zh, 64, K, P, trainable, gl, a.out != nullptr, adj) - corr;
-    else if constexpr (CM == kChainPairs)
-      lp = grad1_pairs<kCS>(z, tl + lane, zh, 64, types, K, P, trainable, gl, a.out != nullptr, adj) - corr;
-    else
-      lp = grad1_packed<kCS>(z, tl + lane, zh, 64, types, K, P, trainable, gl, a.out != nullptr, adj) - corr;
-    {
-      const auto ro = tile_rsrc(a.out && nr > 0 ? a.out + b0 : a.out, a.out ? nr * 4 : 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, lp), ro, lane * 4, 0, kNT);
-      const auto rdy = tile_rsrc(g.grad_y && nr > 0 ? g.grad_y + b0 : g.grad_y, g.grad_y ? nr * 4 : 0);
-      const float gy = norm ? f_div<true>(adj, ystd) : adj;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, gy), rdy, lane * 4, 0, kNT);
-    }
+    const float lp = dense1_grad_chain<CM, SP>(z, tl + lane, zh, a, gl, adj) - nm.corr;
+    store_lp_grad_y(g, sp, lane, lp, norm1_dy(nm, adj));
     // 4. this lane's dt row and db's column sums, from the f32 tile (rows past B carry no
     //    gradient: zeroed first, as in chain_dense1_grad_kernel)
-    if (nr < 64 && lane >= nr) {
-      for (int p = 0; p < P; ++p) tl[p * kCS + lane] = 0.0f;
-    }
+    zero_dt_past_B(tl, P, sp.nr, lane);
     float v[32];  // the dt row
 #pragma unroll
     for (int p = 0; p < 32; ++p) v[p] = (p < NP && p < P) ? tl[p * kCS + lane] : 0.0f;
@@ -745,8 +703,7 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
     // 6. dh^T = W dt^T (B = plane rows): lane (am, ak) ends with dh[16 mt + am][4 ak .. 4 ak + 3];
     //    the six terms small first: (3,1) (2,2) (1,3) (2,1) (1,2) (1,1)
     {
-      const auto rdh = tile_rsrc(g.grad_h && nr > 0 ? g.grad_h + b0 * ghs : g.grad_h,
-                                 g.grad_h && nr > 0 ? ((nr - 1) * ghs + H) * 4 : 0);
+      const auto rdh = span_grad_h(g, sp, H);
       const uint32_t* wr = wpl + am * kSbWRow + 4 * (ak ^ swz_w);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
@@ -763,7 +720,7 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
         acc = mfma_bf16(w2, d1, acc);
         acc = mfma_bf16(w1, d2, acc);
         acc = mfma_bf16(w1, d1, acc);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, acc), rdh, ghoff, mt * ghmt, kNT);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, acc), rdh, ghoff, mt * ghmt, kDenseNT);
       }
     }
     // 7. dW += h^T dt: A = h's parts (split from the transposed reads kept since step 1),
@@ -783,43 +740,19 @@ __global__ void __launch_bounds__(kMaxBlock, (CM == kStaticCache || CM == kStati
         const bf16x8v e1 = tr_frag(bp, bp + 16 * kSbDRow);
         const bf16x8v e2 = tr_frag(bp + 64 * kSbDRow, bp + 80 * kSbDRow);
         const bf16x8v e3 = tr_frag(bp + 128 * kSbDRow, bp + 144 * kSbDRow);
-        f32x4v acc = dw[nt];
+        f32x4v acc = dw[0][nt];
         acc = mfma_bf16(h3, e1, acc);
         acc = mfma_bf16(h2, e2, acc);
         acc = mfma_bf16(h1, e3, acc);
         acc = mfma_bf16(h2, e1, acc);
         acc = mfma_bf16(h1, e2, acc);
-        dw[nt] = mfma_bf16(h1, e1, acc);
+        dw[0][nt] = mfma_bf16(h1, e1, acc);
       }
     }
     wave_lds_sync();  // this tile's LDS reads done before the next tile's writes
   }
   if (g.part == nullptr) return;  // no grad_W / grad_b requested (uniform: every thread returns)
-#pragma unroll
-  for (int nt = 0; nt < NN; ++nt) {
-    db[nt] += __shfl_xor(db[nt], 16);
-    db[nt] += __shfl_xor(db[nt], 32);
-  }
-  const int nWb = H * P + P;
-  __syncthreads();
-  float* mine = lds + wid * wfl;
-#pragma unroll
-  for (int nt = 0; nt < NN; ++nt)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int hr = 4 * ak + i, p = 16 * nt + am;  // C layout: row 4 ak + i, column am
-      if (p < P) mine[hr * P + p] = dw[nt][i];
-    }
-#pragma unroll
-  for (int nt = 0; nt < NN; ++nt)
-    if (ak == 0 && 16 * nt + am < P) mine[H * P + 16 * nt + am] = db[nt];
-  __syncthreads();
-  float* out = g.part + (int64_t)blockIdx.x * nWb;
-  for (int i = tid; i < nWb; i += blockDim.x) {
-    float s = lds[i];
-    for (int w = 1; w < nwave; ++w) s += lds[w * wfl + i];
-    out[i] = s;
-  }
+  dense1_grad_write_partial<1, NN>(g, lds, wfl, dw, db);
 }
 
 // grad_W | grad_b = the sum of the per-workgroup partials (fp64, deterministic): a

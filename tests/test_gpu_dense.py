@@ -168,6 +168,41 @@ def test_posterior_dense_normalised_nobias_and_fallback(gpu):
         check_forward(out.cpu().numpy(), ref64, ref32, f"posterior dense normalised H={H} bias={bias}", kind="dense")
 
 
+@pytest.mark.parametrize("ft,d,H,B,bias,norm,mode", [
+    (("radial",) * 14, 1, 8, 64 * 2 + 5, True, False, "fast"),          # P = 44: three N tiles, ragged last tile
+    (("radial", "radial"), 1, 4, 65, False, False, "fast"),              # no bias
+    (("planar", "radial") * 2, 1, 32, 64, True, True, "fast"),           # y normalisation
+    (("affine", "planar", "radial"), 3, 8, 70, True, False, "fast"),     # posterior_densep_kernel
+    (("affine", "planar", "radial"), 3, 8, 70, True, False, "precise"),  # posterior_dense_kernel
+    (("radial", "planar"), 2, 4, 1, True, False, "fast"),
+])
+def test_posterior_dense_single_draw_is_bitwise_the_forward(gpu, ft, d, H, B, bias, norm, mode):
+    """With one draw the posterior score is log_prob + log 1 - log 1, and the posterior kernels
+    form t with the forward kernels' MFMA order and run the same chain evaluators: value for
+    value (NaN matching NaN) posterior_lse_dense is chain_log_prob_dense, and so is the batch
+    sum.  A guard against the copies of the tile pipeline drifting apart.  (d = 1, H = 16, P <= 32 in fast math is left out: there the forward forms t on
+    split bf16 and the posterior on f32 MFMA, different by design.)"""
+    from normalizingflownetwork_amd import ops
+
+    h, W, b, y, _, _ = _case(ft, d, H, B, seed=H + B + d, bias=bias)
+    ym = np.linspace(0.3, 0.5, d).astype(np.float32) if norm else None
+    ys = np.linspace(1.4, 1.7, d).astype(np.float32) if norm else None
+    yt, ht, Wt = torch.from_numpy(y).cuda(), torch.from_numpy(h).cuda(), torch.from_numpy(W).cuda()
+    bt = None if b is None else torch.from_numpy(b).cuda()
+    prev = ops.set_math_mode(mode)
+    try:
+        fwd, fsum = ops.chain_log_prob_dense(yt, ht, Wt, bt, ft, d, True, ym, ys, want_sum=True)
+        post, psum = ops.posterior_lse_dense(yt, ht, Wt[None], None if bt is None else bt[None], ft, d, True, ym, ys,
+                                             want_sum=True)
+    finally:
+        ops.set_math_mode(prev)
+    fwd, post = fwd.cpu().numpy(), post.cpu().numpy()
+    assert fwd.shape == post.shape == (B,)
+    same = (fwd.view(np.uint32) == post.view(np.uint32)) | (np.isnan(fwd) & np.isnan(post))
+    assert same.all(), f"{(~same).sum()} of {B} values differ, first at {np.flatnonzero(~same)[:4]}"
+    assert np.array_equal(np.float64(fsum.item()), np.float64(psum.item()), equal_nan=True)
+
+
 def test_dense_full_size_c2_sampled(gpu):
     """The fused Dense forward at the C2 batch (2^24 rows, H = 16: the split-bf16 t GEMM) on
     y / h with the bench's scale: 65,536 random rows against the oracle on t = h W + b (the
